@@ -13,9 +13,21 @@ N = 8); a weak-scaling run at 4096 walkers per GPU is reported beside it (``weak
 ``strong_scaling_per_rank`` times the per-rank workloads of N = 2, 4, 8 (2048/1024/512
 walkers) on the one GPU.
 
-Usage: python bench.py [--gpus N --steps K --warmup W].  With N > 1 and no launcher, bench.py
-starts the N ranks itself (torch.distributed.run as a child process, before any GPU call) and
-relays rank 0's line; under an external launcher
+A plain run sets up, warms up, times the K steps of the headline workload and prints the result
+line (the headline's rooflines come from the last timed step's own launches).  Every other
+measurement -- the weak-scaling run beside a strong headline, ``strong_scaling_per_rank``, the
+ccECP / Adam / DMC side configurations and the CPU baselines -- runs only with ``--full`` (where
+the ``--no-*`` options still drop single ones).  ``--dump-outputs DIR`` writes what the last timed
+step returned to its caller as DIR/<name>.npy (rank r > 0: <name>_rank<r>.npy): ``positions``
+[B, 3N] after the step's sweeps and ``local_energy`` [B] in the run's dtype, ``energy_stats``
+(mean, variance) in float64.  Walkers, parameters and Philox counters are seeded, so two runs
+with the same arguments start from the same inputs.  The random-init wavefunction is unbound, so
+a long chain drifts outwards until its fp32 local energies stop being finite; the chain therefore
+restarts from its initial walkers every RESEED_EVERY iterations (longer runs only).
+
+Usage: python bench.py [--gpus N --steps K --warmup W --full --dump-outputs DIR].  With N > 1
+and no launcher, bench.py starts the N ranks itself (torch.distributed.run as a child process,
+before any GPU call) and relays rank 0's line; under an external launcher
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
       --master-port P bench.py --gpus N --steps K --warmup W
 each rank runs directly (a WORLD_SIZE different from --gpus is an error).
@@ -46,6 +58,7 @@ F_EL_N2 = 2.55e6                 # one local-energy evaluation
 PEAK_FP32_TFLOPS = 157.3         # MI355X FP32 vector peak (MI355X_MICROARCH.md)
 PEAK_FP64_TFLOPS = 78.6          # FP64 vector peak (spec)
 PEAK_HBM_GBS = 8000.0
+RESEED_EVERY = 64                # VMC iterations after which the timed chain restarts from its initial walkers
 
 
 # General algorithmic FLOP model of one wavefunction forward for N electrons, A atoms (the side
@@ -104,6 +117,11 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: weak-scaling run, per-rank workloads, "
+                         "ccECP / Adam / DMC side configurations, CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (positions, local_energy, energy_stats) as DIR/<name>.npy")
     ap.add_argument("--walkers", type=int, default=4096, help="walkers per GPU of a weak-scaling run")
     ap.add_argument("--global-walkers", type=int, default=4096,
                     help="strong scaling: this many walkers in total, split over the ranks (SURVEY 8(d): 4096)")
@@ -554,12 +572,23 @@ def main():
     def measure(B, pos0, steps, warmup, tag):
         """warmup + `steps` timed VMC iterations on this rank's B walkers; the job time is the max
         over ranks (barrier + synchronize on both sides of the timed region)."""
-        pos = pos0.to(dev, dtype).contiguous()
+        pos_init = pos0.to(dev, dtype).contiguous()
+        pos = pos_init.clone()
         el = torch.empty(B, dtype=dtype, device=dev)
         seed = 12345 + rank + 7919 * tag
         offset = [0]
+        done = [0]
 
         def iteration(record=None):
+            # the random-init wavefunction binds nothing: the walkers diffuse outwards (max |x| 10 bohr
+            # after 7 iterations, 72 after 310, 97 after 1010) until psi underflows in fp32 and E_L is
+            # NaN for some of them (39 of 4096 after 1010 iterations, none after 310).  So the chain
+            # restarts from the initial walkers every RESEED_EVERY iterations (warm-up included, a
+            # device copy on the launch stream); the Philox counter runs on.  Runs of up to
+            # RESEED_EVERY iterations never restart.
+            if done[0] and done[0] % RESEED_EVERY == 0:
+                pos.copy_(pos_init)
+            done[0] += 1
             if record is not None:
                 record[0].record()
             ctx.mc_step(pos, args.nsteps, args.tstep, seed=seed, offset=offset[0])
@@ -613,7 +642,8 @@ def main():
                 "mc_walker_steps_per_s": total * args.nsteps / (mc_ms_max * 1e-3),
                 "prop_avg_ms": prop_ms / max(prop_n, 1), "prop_n": prop_n,
                 "walk_avg_ms": walk_ms / max(walk_n, 1), "lap_avg_ms": lap_ms / max(lap_n, 1), "lap_n": lap_n,
-                "mean_e": mean_e, "var_e": var_e, "finite": finite}
+                "mean_e": mean_e, "var_e": var_e, "finite": finite,
+                "outputs": {"positions": pos, "local_energy": el, "energy_stats": stats}}
 
     peak = PEAK_FP32_TFLOPS if dtype == torch.float32 else PEAK_FP64_TFLOPS
     lib_sha = _lib.library_sha16()
@@ -665,12 +695,18 @@ def main():
     strong = not args.weak
     B, pos0 = walkers_of(strong)
     head = measure(B, pos0, args.steps, args.warmup, 0)
+    if args.dump_outputs:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, v in head["outputs"].items():
+            a = np.stack([np.asarray(x.detach().cpu()) for x in v]) if isinstance(v, tuple) else v.detach().cpu().numpy()
+            assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+            np.save(os.path.join(args.dump_outputs, name + (f"_rank{rank}" if rank else "") + ".npy"), a)
     weak = None
-    if world > 1 and strong:
+    if args.full and world > 1 and strong:
         Bw, posw = walkers_of(False)
         weak = measure(Bw, posw, args.steps, args.warmup, 1)
     per_rank = {}
-    if world == 1 and not args.no_per_rank and args.system == "N2":
+    if args.full and world == 1 and not args.no_per_rank and args.system == "N2":
         for n in (2, 4, 8):
             Bn = args.global_walkers // n
             pn, _ = init_electrons(1000, None, atoms, charges, spins, args.global_walkers, 1.0)
@@ -725,7 +761,7 @@ def main():
         out["collectives"] = {"process_group": dist_on, "backend": backend if dist_on else None,
                               "forced_at_world_1": bool(args.force_collectives and world == 1),
                               "allreduce_calls_before_side_benches": constants.ALLREDUCE_CALLS}
-        if world == 1 and not args.no_ecp:
+        if args.full and world == 1 and not args.no_ecp:
             try:
                 out["ecp_c_atom"] = ecp_side_bench(dtype, dev, 4096, 5, not args.no_cpu_baseline, pmc_side=pmc_side)
             except Exception as e:  # a side measurement, never a failure of the headline bench
@@ -734,7 +770,7 @@ def main():
                 out["ecp_c2"] = ecp_side_bench(dtype, dev, 4096, 3, False, name="C2_ecp", pmc_side=pmc_side)
             except Exception as e:  # a side measurement, never a failure of the headline bench
                 out["ecp_c2"] = {"error": repr(e)}
-        if world == 1 and not args.no_adam:
+        if args.full and world == 1 and not args.no_adam:
             try:
                 c0 = constants.ALLREDUCE_CALLS
                 out["adam_be_atom"] = adam_side_bench(dtype, dev, 4096, 5, pmc_side=pmc_side)
@@ -743,12 +779,12 @@ def main():
                 out["adam_be_atom"]["allreduce_calls"] = constants.ALLREDUCE_CALLS - c0
             except Exception as e:  # a side measurement, never a failure of the headline bench
                 out["adam_be_atom"] = {"error": repr(e)}
-        if world == 1 and not args.no_adam:
+        if args.full and world == 1 and not args.no_adam:
             try:
                 out["pp_adam_c_atom"] = pp_adam_side_bench(dtype, dev, 4096, 5)
             except Exception as e:  # a side measurement, never a failure of the headline bench
                 out["pp_adam_c_atom"] = {"error": repr(e)}
-        if world == 1 and not args.no_dmc:
+        if args.full and world == 1 and not args.no_dmc:
             try:
                 out["dmc_c_atom"] = dmc_side_bench(dtype, dev, 4096, 5, pmc_side=pmc_side)
             except Exception as e:  # a side measurement, never a failure of the headline bench
@@ -757,7 +793,7 @@ def main():
                 out["dmc_ne_atom"] = dmc_side_bench(dtype, dev, 4096, 5, system="Ne", pmc_side=pmc_side)
             except Exception as e:  # a side measurement, never a failure of the headline bench
                 out["dmc_ne_atom"] = {"error": repr(e)}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(args.system, params, atoms, charges, args.nsteps, args.tstep,
                                                    args.cpu_sample_walkers)

@@ -14,6 +14,7 @@ N2_mc_fp32.npz holds, for each batch size B in {64, 512} (keys suffixed _<B>):
   ratio{t}_{s} [B,N]    |exp(log|psi(x')| - log|psi(x)|)|^2 t_pro  (:100)
   cond{t}_{s} [B,N]     ratio > u  (walkers_accept, :18-25)
   te{t}_{s} [2]         limdrift factors of the walker and the proposal gradients (:60, :80)
+The t = 64 results of B = 512 are kept in N2_mc_fp32_f64_512.npz.
 tests/test_gpu_mc_fp32.py runs the HIP fp32 mc_step on the same inputs.
 """
 import os
@@ -68,7 +69,10 @@ def main(out_dir: str):
         for st in range(2):
             c32, c64 = out[f"cond32_{st}_{B}"], out[f"cond64_{st}_{B}"]
             print(B, st, "fp32 vs fp64 oracle decisions differ:", int((c32 != c64).sum()))
-    np.savez_compressed(os.path.join(out_dir, "N2_mc_fp32.npz"), **out)
+    # the float64 results of the 512-walker batch go to a file of their own (each file < 1 MiB)
+    big = {k: v for k, v in out.items() if k.endswith("_512") and k.split("_")[0][-2:] == "64"}
+    np.savez_compressed(os.path.join(out_dir, "N2_mc_fp32.npz"), **{k: v for k, v in out.items() if k not in big})
+    np.savez_compressed(os.path.join(out_dir, "N2_mc_fp32_f64_512.npz"), **big)
 
 
 if __name__ == "__main__":

@@ -95,7 +95,9 @@ def test_limdrift_factor_guarded_against_huge_and_nonfinite(n):
 
 def _golden_mc(golden_dir):
     import os
-    return np.load(os.path.join(golden_dir, "N2_mc_fp32.npz"))
+    g = dict(np.load(os.path.join(golden_dir, "N2_mc_fp32.npz")))
+    g.update(np.load(os.path.join(golden_dir, "N2_mc_fp32_f64_512.npz")))   # float64 results of B = 512
+    return g
 
 
 def _sweep(ctx, g, B, pos_start, steps, fuse_reduce=1):

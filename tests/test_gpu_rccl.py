@@ -204,8 +204,8 @@ def test_bench_force_collectives_over_rccl_under_torchrun(tmp_path):
     statistics all-reduce and the Be Adam side measurement's fused training step run in RCCL."""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr",
            "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "1",
-           "--force-collectives", "--dist-backend", "nccl", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
-           "--no-ecp", "--no-dmc", "--no-per-rank"]
+           "--force-collectives", "--dist-backend", "nccl", "--steps", "2", "--warmup", "1", "--full",
+           "--no-cpu-baseline", "--no-ecp", "--no-dmc", "--no-per-rank"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=str(tmp_path),
                          env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"))
     assert out.returncode == 0, out.stderr[-3000:]

@@ -111,7 +111,7 @@ def test_two_rank_blocks_equal_single_process(tmp_path, world, b_total):
 def _bench_two_ranks(tmp_path, extra, n=2):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n), "--master-addr",
            "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps",
-           "2", "--warmup", "1", "--no-cpu-baseline", "--no-ecp", "--no-adam", "--no-dmc",
+           "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-ecp", "--no-adam", "--no-dmc",
            "--dist-backend", "gloo"] + extra
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=str(tmp_path),
                          env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"))
@@ -153,7 +153,7 @@ def test_bench_gpus_flag_spawns_ranks_without_launcher(tmp_path):
     must start the two ranks itself (torch.distributed.run as a child, before any GPU call) and relay
     rank 0's line -- not silently run one rank (VERDICT r4 weak #2)."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dist-backend", "gloo", "--steps", "2",
-           "--warmup", "1", "--no-ecp", "--no-adam", "--no-dmc", "--no-cpu-baseline", "--global-walkers", "1024",
+           "--warmup", "1", "--full", "--no-ecp", "--no-adam", "--no-dmc", "--no-cpu-baseline", "--global-walkers", "1024",
            "--walkers", "256"]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=str(tmp_path),

@@ -338,4 +338,5 @@ def make_loss(network, local_energy, clip_local_energy: float = 0.0, clip_from_m
     total_energy.value_and_pmean_grad = value_and_pmean_grad
     total_energy.unflatten = lambda params, flat: _unflatten_like(params, flat)
     total_energy._aiqmc_network = net
+    total_energy.complex_output = bool(complex_output)   # read by Optimizer.sr (phase Jacobian in S)
     return total_energy

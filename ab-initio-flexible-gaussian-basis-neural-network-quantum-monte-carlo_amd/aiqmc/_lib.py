@@ -35,7 +35,7 @@ EXPORTED_SYMBOLS = (
     "aiqmc_dmc_weights_ex", "aiqmc_dmc_cut_minima", "aiqmc_orbitals", "aiqmc_debug_set_ablate", "aiqmc_debug_set_fuse_accept", "aiqmc_debug_set_walker_pivots", "aiqmc_debug_set_packed_walkers", "aiqmc_debug_set_quad_pivoted", "aiqmc_debug_set_lap_waves",
     "aiqmc_debug_set_fuse_reduce", "aiqmc_energy_stats", "aiqmc_energy_stats_final",
     "aiqmc_debug_limdrift_factor", "aiqmc_debug_launch_lds", "aiqmc_loss_weights",
-    "aiqmc_param_grad_weighted", "aiqmc_loss_level", "aiqmc_loss_pack", "aiqmc_loss_final",
+    "aiqmc_param_grad_weighted", "aiqmc_loss_level", "aiqmc_loss_pack", "aiqmc_loss_final", "aiqmc_sr_gram",
 )
 
 PROF_MC_PROPOSAL = 0   # proposal value+gradient launches of aiqmc_mc_step
@@ -43,6 +43,7 @@ PROF_MC_WALKER = 1     # walker gradient launches of aiqmc_mc_step
 PROF_LOCAL_ENERGY = 2  # aiqmc_local_energy launches
 PROF_ECP_QUAD = 3      # value-only launches over the ECP quadrature configurations
 ECP_NQ = 50            # quadrature points per (electron, atom) (pseudopotential.py:181-225)
+SR_CHUNK = 256         # AIQMC_SR_CHUNK: walkers summed in the operand dtype before the fp64 combine (aiqmc_sr_gram)
 
 
 class AiqmcCfg(ctypes.Structure):
@@ -175,6 +176,8 @@ def load() -> ctypes.CDLL:
     lib.aiqmc_loss_level.argtypes = [i32, vp, vp, i32, i64, vp, vp, dbl, dbl, i32, vp, vp, vp, vp, vp, vp]
     lib.aiqmc_loss_pack.argtypes = [vp, vp, vp, i32, i32, vp, vp]
     lib.aiqmc_loss_final.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]
+    lib.aiqmc_sr_gram.argtypes = [vp, vp, i32, i64, i32, vp, vp, vp, i32, vp]
+    lib.aiqmc_sr_gram.restype = ctypes.c_int
     lib.aiqmc_last_error.restype = ctypes.c_char_p
     lib.aiqmc_supported_shapes.restype = ctypes.c_char_p
     for name in ("aiqmc_create", "aiqmc_destroy", "aiqmc_set_params", "aiqmc_set_params_device", "aiqmc_logpsi",
@@ -313,6 +316,45 @@ def loss_final(L1: torch.Tensor, L3: torch.Tensor, P: int, g0: bool, center_at_c
                                   AIQMC_F32 if dtype == torch.float32 else AIQMC_F64, _ptr(grad), _ptr(stats),
                                   _stream(L1.device)), "aiqmc_loss_final")
     return grad, stats
+
+
+def sr_gram(o_re: torch.Tensor, o_im: Optional[torch.Tensor] = None, center_re: Optional[torch.Tensor] = None,
+            center_im: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+            accumulate: bool = False) -> torch.Tensor:
+    """aiqmc_sr_gram on per-walker Jacobians [B, P] (float32/float64 device tensors; o_im: the
+    phase Jacobian or None): the float64 device vector [G (P*P), s_re (P), s_im (P), n] of the
+    Gram product centred at center_re / center_im ([P], converted to the Jacobian's dtype; None =
+    0).  `out`: written in place, added to with accumulate=True (walker blocks)."""
+    if not (o_re.is_cuda and o_re.dim() == 2 and o_re.dtype in (torch.float32, torch.float64)):
+        raise ValueError("sr_gram: a [B, P] float32/float64 device tensor is required")
+    B, P = o_re.shape
+    if P <= 0:
+        raise ValueError("sr_gram: P must be positive")
+    dev, dt = o_re.device, o_re.dtype
+
+    def same(t, shape, what):
+        if t is None:
+            return None
+        t = t.to(dev, dt).contiguous()
+        if tuple(t.shape) != shape:
+            raise ValueError(f"sr_gram: {what} must have shape {shape}, got {tuple(t.shape)}")
+        return t
+
+    a = o_re.contiguous()
+    b = same(o_im, (B, P), "o_im")
+    cr, ci = same(center_re, (P,), "center_re"), same(center_im, (P,), "center_im")
+    n_out = P * P + 2 * P + 1
+    if out is None:
+        if accumulate:
+            raise ValueError("sr_gram: accumulate needs the vector to add to")
+        out = torch.empty(n_out, dtype=torch.float64, device=dev)
+    elif not (out.is_cuda and out.device == dev and out.dtype == torch.float64 and out.is_contiguous()
+              and out.numel() == n_out):
+        raise ValueError(f"sr_gram: out must be a contiguous float64 device vector of {n_out} entries")
+    with torch.cuda.device(dev):
+        check(load().aiqmc_sr_gram(_ptr(a), _ptr(b), _dt(a), B, P, _ptr(cr), _ptr(ci), _ptr(out),
+                                   1 if accumulate else 0, _stream(dev)), "aiqmc_sr_gram")
+    return out
 
 
 def energy_stats_final(out: torch.Tensor) -> torch.Tensor:

@@ -300,6 +300,24 @@ int aiqmc_loss_pack(const void* g, const void* gp, const void* g0, int32_t dtype
 int aiqmc_loss_final(const double* L1, const double* L3, int32_t P, int32_t g0, int32_t center_at_clipped,
                      int32_t world, int32_t dtype, void* grad, double* stats, void* stream);
 
+/* The centred Gram product of stochastic reconfiguration (aiqmc/Optimizer/sr.py): for the
+ * per-walker Jacobians o_re = d log|psi| / d theta and o_im = d phase / d theta ([B][P] row-major
+ * device arrays of `dtype`, as aiqmc_logpsi_param_grad / aiqmc_phase_param_grad return them
+ * without weights; o_im NULL = absent) and a centre c (center_re / center_im: [P] device arrays
+ * of the same `dtype`, NULL = 0), out (device fp64, P*P + 2P + 1 entries, the vector for ONE sum
+ * all-reduce) receives
+ *   G[P][P] = sum_b (o_re_b - c_re)(o_re_b - c_re)^T + (o_im_b - c_im)(o_im_b - c_im)^T   (full, symmetric)
+ *   s_re[P] = sum_b (o_re_b - c_re),  s_im[P] = sum_b (o_im_b - c_im),  n = B,
+ * from which the covariance for ANY centre is G/n - (s_re s_re^T + s_im s_im^T)/n^2.
+ * accumulate != 0 adds into out instead of overwriting it (walker blocks).  Context-free; runs on
+ * the current device.  One workgroup owns a 64 x 64 tile of G for all walkers (no atomics: the
+ * same bits run to run, G == G^T bitwise); sums run in `dtype` on the matrix cores over chunks of
+ * AIQMC_SR_CHUNK walkers (re and im apart), the chunks are added in fp64 in ascending order.
+ * B == 0 writes (or adds) zeros. */
+#define AIQMC_SR_CHUNK 256
+int aiqmc_sr_gram(const void* o_re, const void* o_im, int32_t dtype, int64_t B, int32_t P,
+                  const void* center_re, const void* center_im, double* out, int32_t accumulate, void* stream);
+
 /* Optional HIP-event timing of the hot kernels, recorded on the caller's
  * stream around each launch while enabled.  Slots: 0 = proposal
  * value+gradient launches of aiqmc_mc_step, 1 = walker gradient launches of

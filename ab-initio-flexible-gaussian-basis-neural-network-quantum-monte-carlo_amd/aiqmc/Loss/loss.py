@@ -94,7 +94,9 @@ def _host_level(level, er, ei, L1=None, L2=None, clip=0.0, wscale=1.0, g0=False,
 def _mean_var(L1):
     ntot = L1[4]
     mr, mi = L1[1] / ntot, L1[2] / ntot
-    between = torch.clamp(L1[3] - ntot * mr * mr - ntot * mi * mi, min=0.0)
+    # subtract the sum as level 1 forms it: (a + b) - a - b is not 0 in floating point, and one
+    # rank's between-term must be (one complex energy: variance 0, not 1e-11)
+    between = torch.clamp(L1[3] - (ntot * mr * mr + ntot * mi * mi), min=0.0)
     return mr, mi, (L1[0] + between) / ntot
 
 
@@ -115,6 +117,15 @@ def fused_levels(e_l: torch.Tensor, grad_fn, clip_local_energy: float, center_at
     gradients of this rank's walkers.  Returns (loss, variance, clipped_energy, grad, imag_count).
     Device energies run the HIP level kernels (aiqmc_loss_level / _pack / _final); host energies
     the same formulas in torch.
+
+    Deviation from the reference for UNEQUAL rank batches: the levels pool over walkers
+    (E = sum_r n_r m_r / sum_r n_r; the variance, the TV window and the clipped mean are divided by
+    the total walker count), while the reference's constants.pmean(jnp.mean(.)) (loss.py:107,
+    :206, :208) is the mean of the rank means, every rank weighing the same whatever its batch.
+    The two are the same numbers when every rank holds the same number of walkers, as the
+    reference's pmap requires; with unequal batches this function returns the pooled-batch
+    values (tests/test_gpu_reductions.py, tests/test_loss_levels_host.py).  wscale is (1 or 2) / (this
+    rank's batch), so the gradient, too, is the pooled one only for equal batches.
     """
     cplx = torch.is_complex(e_l)
     er = (e_l.real if cplx else e_l).contiguous().reshape(-1)

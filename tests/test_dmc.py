@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+import test_gpu_reductions as _red     # the comb inputs of the GPU comparisons
 from oracle import dmc as odmc
 
 
@@ -19,6 +20,41 @@ def test_comb_closed_form():
     assert wn == 1.0
     wn, idx = odmc.branch(np.array([3.0, 0.0, 0.5, 0.5]), 0.0)
     np.testing.assert_array_equal(idx, [0, 0, 0, 0])   # cumsum [3, 3, 3.5, 4], targets [0, 1, 2, 3]
+
+
+@pytest.mark.parametrize("u", [0.0, 0.37, 0.999999])
+@pytest.mark.parametrize("n", _red.COMB_N)
+@pytest.mark.parametrize("dtype", _red.DTYPES, ids=_red.DT_IDS)
+def test_comb_inputs_are_well_separated(dtype, n, u):
+    """The precondition of test_gpu_reductions.py's exact index equality (reference alone): no
+    comb target within 1e-10 wtot of a cumulative-sum value, so fp64 rounding of the cumulative
+    sum (a few 1e-15 wtot between the kernel's blocked scan and np.cumsum) cannot move an index."""
+    assert _red._comb_gap(_red._comb_weights(n, dtype), u) >= 1e-10
+
+
+@pytest.mark.parametrize("u", [0.0, 0.5, 0.75])
+@pytest.mark.parametrize("n", _red.TIE_N)
+def test_oracle_comb_tie_rule_is_left_search(n, u):
+    """oracle.dmc.branch on the integer-weight inputs (hundreds of targets exactly ON a
+    cumulative-sum value) equals a left search done in Python integers: the first k with
+    cumsum[k] >= target.  Pins the oracle's tie rule (np.searchsorted side='left', branch.py:27)."""
+    w = _red._tie_weights(n)
+    cs = [int(v) for v in np.cumsum(w)]
+    tt = _red._tie_targets_int(n, u)
+    want = [0] * n
+    k = 0
+    for j in sorted(range(n), key=lambda j: tt[j]):    # one forward sweep over the sorted targets
+        while cs[k] < tt[j]:
+            k += 1
+        want[j] = k
+    if n == 1024:                                         # and the literal scan per target
+        assert want == [next(k for k in range(n) if cs[k] >= t) for t in tt]
+    wn, idx = odmc.branch(w.astype(np.float64), u)
+    assert wn == 2.0
+    assert idx.tolist() == want
+    on_cs = set(cs)
+    assert sum(t in on_cs for t in tt) >= n // 8         # the ties are really there
+    assert all(w[k] != 0 for k in want)                   # a zero-weight walker is never selected
 
 
 def test_comput_S_single_global_cut():

@@ -93,6 +93,23 @@ def test_limdrift_factor_guarded_against_huge_and_nonfinite(n):
             assert abs(f[0] - float(te32)) <= 1e-5 * abs(float(te32)), (name, f[0], float(te32))
 
 
+@pytest.mark.parametrize("n", [1, 1023, 1025, 8191, 8193, 32767, 32769, 40001])
+def test_limdrift_factor_sizes_with_a_tail(n):
+    """k_taueff (mode 2) walks 32 x 1024, then 8 x 1024 elements per round, then up to 7 guarded
+    steps; the sizes above leave a partial last step in each of the three loops (the sizes of the
+    test above are all multiples of 64 x 14).  Ordinary inputs, all three reductions."""
+    _, ctx = _ctx()
+    x = np.random.default_rng(n).gamma(2.0, 20.0, n).astype(np.float32)
+    ref = _reference_factor(x, TAU)
+    xt = torch.tensor(x, device="cuda")
+    f = [ctx.limdrift_factor(xt, TAU, m) for m in (0, 1, 2)]
+    print(n, "reference", ref, "fused / partials / fp64 tree", f)
+    assert all(math.isfinite(v) for v in f), f
+    assert f[0] == f[1], f
+    for v in f:
+        assert abs(v - ref) <= 1e-6 * abs(ref) + 1e-30, (v, ref)
+
+
 def _golden_mc(golden_dir):
     import os
     g = dict(np.load(os.path.join(golden_dir, "N2_mc_fp32.npz")))

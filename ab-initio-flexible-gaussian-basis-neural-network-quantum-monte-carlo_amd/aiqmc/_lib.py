@@ -36,6 +36,7 @@ EXPORTED_SYMBOLS = (
     "aiqmc_debug_set_fuse_reduce", "aiqmc_energy_stats", "aiqmc_energy_stats_final",
     "aiqmc_debug_limdrift_factor", "aiqmc_debug_launch_lds", "aiqmc_loss_weights",
     "aiqmc_param_grad_weighted", "aiqmc_loss_level", "aiqmc_loss_pack", "aiqmc_loss_final", "aiqmc_sr_gram",
+    "aiqmc_spin_squared", "aiqmc_dipole", "aiqmc_debug_set_obs_chunk",
 )
 
 PROF_MC_PROPOSAL = 0   # proposal value+gradient launches of aiqmc_mc_step
@@ -178,6 +179,12 @@ def load() -> ctypes.CDLL:
     lib.aiqmc_loss_final.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]
     lib.aiqmc_sr_gram.argtypes = [vp, vp, i32, i64, i32, vp, vp, vp, i32, vp]
     lib.aiqmc_sr_gram.restype = ctypes.c_int
+    lib.aiqmc_spin_squared.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp]
+    lib.aiqmc_spin_squared.restype = ctypes.c_int
+    lib.aiqmc_dipole.argtypes = [vp, vp, i32, vp, vp]
+    lib.aiqmc_dipole.restype = ctypes.c_int
+    lib.aiqmc_debug_set_obs_chunk.argtypes = [vp, i32]
+    lib.aiqmc_debug_set_obs_chunk.restype = ctypes.c_int
     lib.aiqmc_last_error.restype = ctypes.c_char_p
     lib.aiqmc_supported_shapes.restype = ctypes.c_char_p
     for name in ("aiqmc_create", "aiqmc_destroy", "aiqmc_set_params", "aiqmc_set_params_device", "aiqmc_logpsi",
@@ -376,6 +383,7 @@ class Context:
         self.device = torch.device("cuda", device)
         self.N = int(nelectrons)
         self.A = int(natoms)
+        self.nspins = (int(nspins[0]), int(nspins[1]))
         self._keep = []
 
         def dbl(a):
@@ -486,6 +494,45 @@ class Context:
         check(self._lib.aiqmc_orbitals(self._h, _ptr(p), B, _ptr(out), None, None, _stream(self.device)),
               "aiqmc_orbitals")
         return torch.view_as_complex(out)
+
+    # -- observables (aiqmc/observables.py) ---------------------------------
+    def spin_squared(self, pos: torch.Tensor, want_pairs: bool = False, chunk: Optional[int] = None):
+        """The S^2 estimator of each walker for this context's fixed spin assignment
+        (aiqmc_spin_squared): a complex tensor [B] (complex64 for a float32 context; the imaginary
+        part averages to zero).  want_pairs: also (dlogabs, dphase) [B, n_up, n_down], log|psi| and
+        phase at the walker with up slot i and down slot j exchanged minus those at the walker.
+        chunk: configurations per value launch for this call (diagnostics; default 4096, whole
+        walkers, at least one); the result does not depend on it."""
+        p = self._pos(pos)
+        B = p.shape[0]
+        nup, ndn = self.nspins
+        re = torch.empty(B, dtype=self.dtype, device=self.device)
+        im = torch.empty(B, dtype=self.dtype, device=self.device)
+        dl = torch.empty(B, nup, ndn, dtype=self.dtype, device=self.device) if want_pairs else None
+        dp = torch.empty(B, nup, ndn, dtype=self.dtype, device=self.device) if want_pairs else None
+        if chunk is not None:
+            if int(chunk) <= 0:
+                raise ValueError("chunk must be positive")
+            check(self._lib.aiqmc_debug_set_obs_chunk(self._h, int(chunk)), "aiqmc_debug_set_obs_chunk")
+        try:
+            with torch.cuda.device(self.device):
+                check(self._lib.aiqmc_spin_squared(self._h, _ptr(p), B, _ptr(re), _ptr(im), _ptr(dl), _ptr(dp),
+                                                   _stream(self.device)), "aiqmc_spin_squared")
+        finally:
+            if chunk is not None:
+                self._lib.aiqmc_debug_set_obs_chunk(self._h, 0)
+        s2 = torch.complex(re, im)
+        return (s2, dl, dp) if want_pairs else s2
+
+    def dipole(self, pos: torch.Tensor) -> torch.Tensor:
+        """Dipole moment [B, 3] in atomic units: sum_a Z_a R_a - sum_i r_i (aiqmc_dipole; Z_a the
+        context charges, Z_eff under an ECP)."""
+        p = self._pos(pos)
+        B = p.shape[0]
+        mu = torch.empty(B, 3, dtype=self.dtype, device=self.device)
+        with torch.cuda.device(self.device):
+            check(self._lib.aiqmc_dipole(self._h, _ptr(p), B, _ptr(mu), _stream(self.device)), "aiqmc_dipole")
+        return mu
 
     def logpsi_grad(self, pos: torch.Tensor):
         p = self._pos(pos)

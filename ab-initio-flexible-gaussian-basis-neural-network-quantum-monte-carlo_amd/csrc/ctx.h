@@ -78,6 +78,12 @@ struct aiqmc_ctx {
   void* d_pgr = nullptr;            // [nkern] weighted sum
   int pg_B = 0;
   int pg_nw = 0;                     // weighted rows d_pgr holds before its chunk sums
+  // observables (aiqmc_spin_squared, observables.hip): one chunk of exchanged configurations
+  // [obs_n][3N], their log|psi| and phase [obs_n], and the value launch's walker cache
+  void *d_obs_x = nullptr, *d_obs_lp = nullptr, *d_obs_ph = nullptr, *d_obs_wc = nullptr;
+  int obs_n = 0;                     // capacity in configurations
+  int obs_chunk = 4096;              // configurations per value launch (aiqmc_debug_set_obs_chunk)
+  int64_t obs_bytes = 0;
   // optional per-kernel HIP-event timing (aiqmc_profile_*): slot -> recorded (start, stop) pairs
   bool prof = false;
   std::vector<hipEvent_t> ev_free;
@@ -107,5 +113,9 @@ struct ShapeOps {
   int dyn_lds[2][6];
   int wg_waves[2][6];
 };
+
+// shared between aiqmc.hip and observables.hip
+bool aiqmc_shape_ops(int N, int A, ShapeOps* ops);   // aiqmc.hip: the dispatch table of a built shape
+void aiqmc_obs_free(aiqmc_ctx* c);                   // observables.hip: releases the observables workspace
 
 

@@ -318,6 +318,30 @@ int aiqmc_loss_final(const double* L1, const double* L3, int32_t P, int32_t g0, 
 int aiqmc_sr_gram(const void* o_re, const void* o_im, int32_t dtype, int64_t B, int32_t P,
                   const void* center_re, const void* center_im, double* out, int32_t accumulate, void* stream);
 
+/* Spin-squared estimator for the fixed spin assignment of the context (the assign_spin=True
+ * branch of ferminet/observables.py:98-227 make_s2, restated for the slot-based spin tables):
+ *   S2_L(x) = (na - nb)/2 ((na - nb)/2 + 1) + nb - sum_{i in up} sum_{j in down} psi(x_{i<->j}) / psi(x),
+ * na = max(n_up, n_down), nb = min(n_up, n_down), x_{i<->j} = x with the coordinates of electron
+ * slots i and j exchanged (the spin labels stay on the slots).  psi is complex, so the ratio is
+ * exp(dlogabs) (cos dphase + i sin dphase): s2_re[B], s2_im[B] (ctx dtype) receive the real and
+ * imaginary parts (the latter averages to zero).  dlogabs / dphase (optional, [B][n_up][n_down],
+ * i over spin_up_indices in the outer index, j over spin_down_indices in the inner one): log|psi|
+ * and phase at the exchanged configuration minus those at the walker.  Nothing is clamped: a
+ * walker on a node gives an infinite or NaN ratio.  Cost: n_up n_down + 1 value forwards per
+ * walker, launched in chunks whose workspace does not depend on B; sums in a fixed order (the
+ * same bits run to run).  B == 0 writes nothing.  Needs aiqmc_set_params. */
+int aiqmc_spin_squared(aiqmc_ctx* ctx, const void* pos, int32_t B, void* s2_re, void* s2_im, void* dlogabs,
+                       void* dphase, void* stream);
+
+/* Dipole moment of B configurations in atomic units (ferminet/observables.py:230-272 make_dipole
+ * with the nuclear term): mu[B][3] = sum_a Z_a R_a - sum_i r_i, Z_a the context charges (Z_eff
+ * under an ECP). */
+int aiqmc_dipole(aiqmc_ctx* ctx, const void* pos, int32_t B, void* mu, void* stream);
+
+/* Diagnostics: configurations per value launch of aiqmc_spin_squared (default 4096; nconf <= 0
+ * restores it).  A chunk holds whole walkers, at least one.  Results do not depend on it. */
+int aiqmc_debug_set_obs_chunk(aiqmc_ctx* ctx, int32_t nconf);
+
 /* Optional HIP-event timing of the hot kernels, recorded on the caller's
  * stream around each launch while enabled.  Slots: 0 = proposal
  * value+gradient launches of aiqmc_mc_step, 1 = walker gradient launches of

@@ -26,20 +26,13 @@
 #include <string>
 
 #include "aiqmc.h"
-#include "ctx.h"
+#include "api_util.h"
 
 using namespace aq;
 
 namespace {
 
 constexpr int OBS_CHUNK_DEFAULT = 4096;   // configurations per value launch
-
-int fail(int code, const std::string& m) { return aiqmc_fail(code, m); }
-#define OBS_HIPCHK(x)                                                                      \
-  do {                                                                                     \
-    hipError_t e_ = (x);                                                                   \
-    if (e_ != hipSuccess) return fail(AIQMC_EHIP, std::string(#x) + ": " + hipGetErrorString(e_)); \
-  } while (0)
 
 // x[q][3N] for q = w (K + 1) + p < nconf from walkers pos[b0 + w][3N]; rowsrc: up slots then down slots
 template <typename T>
@@ -119,20 +112,13 @@ __global__ __launch_bounds__(256) void k_dipole(const T* __restrict__ pos, int N
   mu[t] = (T)(c == 0 ? n0 : (c == 1 ? n1 : n2)) - s;
 }
 
+// the workspace of one chunk of nconf configurations
 int obs_ensure(aiqmc_ctx* c, int nconf, const ShapeOps& ops) {
-  if (c->obs_n >= nconf) return 0;
-  aiqmc_obs_free(c);
-  const size_t s = c->dtype == AIQMC_F32 ? 4 : 8;
-  const size_t bytes[4] = {(size_t)nconf * 3 * c->N * s, (size_t)nconf * s, (size_t)nconf * s,
-                           (size_t)nconf * (size_t)ops.wcache_n * s};
-  void** ptrs[4] = {&c->d_obs_x, &c->d_obs_lp, &c->d_obs_ph, &c->d_obs_wc};
-  int64_t tot = 0;
-  for (int k = 0; k < 4; ++k) {
-    OBS_HIPCHK(hipMalloc(ptrs[k], bytes[k]));
-    tot += (int64_t)bytes[k];
-  }
-  c->obs_n = nconf;
-  c->obs_bytes = tot;
+  const size_t s = elem_size(c), n = (size_t)nconf;
+  HIPCHK(c->d_obs_x.reserve(n * 3 * c->N * s));
+  HIPCHK(c->d_obs_lp.reserve(n * s));
+  HIPCHK(c->d_obs_ph.reserve(n * s));
+  HIPCHK(c->d_obs_wc.reserve(n * ops.wcache_n * s));
   return 0;
 }
 
@@ -152,30 +138,14 @@ void s2_reduce_launch(int G, int nw, const void* lp, const void* ph, int K, int 
 
 }  // namespace
 
-void aiqmc_obs_free(aiqmc_ctx* c) {
-  void* ps[] = {c->d_obs_x, c->d_obs_lp, c->d_obs_ph, c->d_obs_wc};
-  for (void* p : ps)
-    if (p) (void)hipFree(p);
-  c->d_obs_x = c->d_obs_lp = c->d_obs_ph = c->d_obs_wc = nullptr;
-  c->obs_n = 0;
-  c->obs_bytes = 0;
-}
-
 extern "C" {
 
 int aiqmc_spin_squared(aiqmc_ctx* c, const void* pos, int32_t B, void* s2_re, void* s2_im, void* dlogabs,
                        void* dphase, void* stream) {
-  if (!c) return fail(AIQMC_EINVAL, "null context");
-  if (!c->params_set) return fail(AIQMC_ESTATE, "aiqmc_set_params has not been called");
-  if (B < 0) return fail(AIQMC_EINVAL, "negative batch");
-  if (B == 0) return AIQMC_OK;
-  if (!pos) return fail(AIQMC_EINVAL, "null positions");
+  AIQMC_ENTER(c, pos, B, ops);
   if (!s2_re || !s2_im) return fail(AIQMC_EINVAL, "null s2_re / s2_im");
   const int K = c->nup * c->ndn;
   if ((int64_t)B * K > INT32_MAX) return fail(AIQMC_EINVAL, "too many exchanged configurations for one call");
-  OBS_HIPCHK(hipSetDevice(c->device));
-  ShapeOps ops;
-  if (!aiqmc_shape_ops(c->N, c->A, &ops)) return fail(AIQMC_EUNSUPPORTED, "no kernel instantiation for this shape");
   int W = c->obs_chunk / (K + 1);   // walkers per chunk
   if (W < 1) W = 1;
   if (W > B) W = B;
@@ -187,36 +157,36 @@ int aiqmc_spin_squared(aiqmc_ctx* c, const void* pos, int32_t B, void* s2_re, vo
   while (G < K) G *= 2;
   hipStream_t s = (hipStream_t)stream;
   const bool f32 = c->dtype == AIQMC_F32;
+  const int* rowsrc = c->d_rowsrc.as<int>();
+  void *lp = c->d_obs_lp.as(), *ph = c->d_obs_ph.as();
   for (int b0 = 0; b0 < B; b0 += W) {
     const int nw = B - b0 < W ? B - b0 : W;
     const int nconf = nw * (K + 1);
     const unsigned nbx = (unsigned)(((int64_t)nconf * c->N + 255) / 256);
     if (f32)
-      k_s2_exchange<float><<<dim3(nbx), dim3(256), 0, s>>>((const float*)pos, c->d_rowsrc, c->N, c->nup, c->ndn, b0,
-                                                           nconf, (float*)c->d_obs_x);
+      k_s2_exchange<float><<<dim3(nbx), dim3(256), 0, s>>>((const float*)pos, rowsrc, c->N, c->nup, c->ndn, b0, nconf,
+                                                           c->d_obs_x.as<float>());
     else
-      k_s2_exchange<double><<<dim3(nbx), dim3(256), 0, s>>>((const double*)pos, c->d_rowsrc, c->N, c->nup, c->ndn, b0,
-                                                            nconf, (double*)c->d_obs_x);
+      k_s2_exchange<double><<<dim3(nbx), dim3(256), 0, s>>>((const double*)pos, rowsrc, c->N, c->nup, c->ndn, b0,
+                                                            nconf, c->d_obs_x.as<double>());
     // the arguments of aiqmc_logpsi
     KArgs ka;
     std::memset(&ka, 0, sizeof(ka));
     ka.nup = c->nup;
-    ka.rowsrc = c->d_rowsrc;
-    ka.prm = c->d_prm;
+    ka.rowsrc = rowsrc;
+    ka.prm = c->d_prm.as();
     ka.one_wave = c->packed_walkers ? 0 : 1;
     ka.quad_pivoted = c->quad_pivoted;
     ka.nconf = nconf;
-    ka.pos = c->d_obs_x;
-    ka.logabs = c->d_obs_lp;
-    ka.phase = c->d_obs_ph;
-    ka.wcache = c->d_obs_wc;
+    ka.pos = c->d_obs_x.as();
+    ka.logabs = lp;
+    ka.phase = ph;
+    ka.wcache = c->d_obs_wc.as();
     ops.walker(c->dtype, MODE_GRAD, ka, nconf, s);
-    if (f32)
-      s2_reduce_launch<float>(G, nw, c->d_obs_lp, c->d_obs_ph, K, b0, diag, s2_re, s2_im, dlogabs, dphase, s);
-    else
-      s2_reduce_launch<double>(G, nw, c->d_obs_lp, c->d_obs_ph, K, b0, diag, s2_re, s2_im, dlogabs, dphase, s);
+    if (f32) s2_reduce_launch<float>(G, nw, lp, ph, K, b0, diag, s2_re, s2_im, dlogabs, dphase, s);
+    else s2_reduce_launch<double>(G, nw, lp, ph, K, b0, diag, s2_re, s2_im, dlogabs, dphase, s);
   }
-  OBS_HIPCHK(hipGetLastError());
+  HIPCHK(hipGetLastError());
   return AIQMC_OK;
 }
 
@@ -226,7 +196,7 @@ int aiqmc_dipole(aiqmc_ctx* c, const void* pos, int32_t B, void* mu, void* strea
   if (B == 0) return AIQMC_OK;
   if (!pos) return fail(AIQMC_EINVAL, "null positions");
   if (!mu) return fail(AIQMC_EINVAL, "null mu");
-  OBS_HIPCHK(hipSetDevice(c->device));
+  HIPCHK(hipSetDevice(c->device));
   double nuc[3] = {0.0, 0.0, 0.0};
   for (int a = 0; a < c->A; ++a)
     for (int d = 0; d < 3; ++d) nuc[d] += c->charges[a] * c->atoms[3 * a + d];
@@ -236,7 +206,7 @@ int aiqmc_dipole(aiqmc_ctx* c, const void* pos, int32_t B, void* mu, void* strea
     k_dipole<float><<<dim3(nbx), dim3(256), 0, s>>>((const float*)pos, c->N, B, nuc[0], nuc[1], nuc[2], (float*)mu);
   else
     k_dipole<double><<<dim3(nbx), dim3(256), 0, s>>>((const double*)pos, c->N, B, nuc[0], nuc[1], nuc[2], (double*)mu);
-  OBS_HIPCHK(hipGetLastError());
+  HIPCHK(hipGetLastError());
   return AIQMC_OK;
 }
 

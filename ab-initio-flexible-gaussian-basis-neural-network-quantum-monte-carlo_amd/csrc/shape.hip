@@ -6,7 +6,7 @@
 #include <cstdlib>
 #include <cstring>
 
-#include "ctx.h"
+#include "api_util.h"
 #include "walker_lap.h"
 #include "quad_small.h"
 #include "walker_pgrad.h"
@@ -16,8 +16,6 @@ using namespace aq;
 #ifndef AQ_N
 #error "compile with -DAQ_N=<electrons> -DAQ_A=<atoms>"
 #endif
-
-static int fail(int code, const std::string& m) { return aiqmc_fail(code, m); }
 
 // One thread per (walker b, electron i): the acceptance of walkers_update (VMCmcstep.py:80-106)
 // for the last sweep of aiqmc_mc_step (earlier sweeps fuse it into the next walker launch) and

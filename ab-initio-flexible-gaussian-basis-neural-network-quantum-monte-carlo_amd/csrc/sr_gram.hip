@@ -20,7 +20,7 @@
 #include <string>
 
 #include "aiqmc.h"
-#include "ctx.h"
+#include "api_util.h"
 
 static_assert(AIQMC_SR_CHUNK % 4 == 0, "SR_CHUNK is a whole number of K = 4 MFMA steps");
 
@@ -220,9 +220,9 @@ extern "C" {
 
 int aiqmc_sr_gram(const void* o_re, const void* o_im, int32_t dtype, int64_t B, int32_t P, const void* center_re,
                   const void* center_im, double* out, int32_t accumulate, void* stream) {
-  if (!out || P <= 0 || B < 0) return aiqmc_fail(AIQMC_EINVAL, "sr_gram: null out, P <= 0 or B < 0");
-  if (B > 0 && !o_re) return aiqmc_fail(AIQMC_EINVAL, "sr_gram: null o_re");
-  if (P > 32768) return aiqmc_fail(AIQMC_EINVAL, "sr_gram: P > 32768");
+  if (!out || P <= 0 || B < 0) return fail(AIQMC_EINVAL, "sr_gram: null out, P <= 0 or B < 0");
+  if (B > 0 && !o_re) return fail(AIQMC_EINVAL, "sr_gram: null o_re");
+  if (P > 32768) return fail(AIQMC_EINVAL, "sr_gram: P > 32768");
   hipStream_t s = (hipStream_t)stream;
   const int nt = (P + SR_TILE - 1) / SR_TILE;
   const dim3 gr(nt, nt);
@@ -233,9 +233,9 @@ int aiqmc_sr_gram(const void* o_re, const void* o_im, int32_t dtype, int64_t B, 
     k_sr_gram<double><<<gr, dim3(256), 0, s>>>((const double*)o_re, (const double*)o_im, B, P,
                                                (const double*)center_re, (const double*)center_im, out, accumulate);
   else
-    return aiqmc_fail(AIQMC_EINVAL, "dtype must be AIQMC_F32 or AIQMC_F64");
+    return fail(AIQMC_EINVAL, "dtype must be AIQMC_F32 or AIQMC_F64");
   const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return aiqmc_fail(AIQMC_EHIP, std::string("sr_gram: ") + hipGetErrorString(e));
+  if (e != hipSuccess) return fail(AIQMC_EHIP, std::string("sr_gram: ") + hipGetErrorString(e));
   return AIQMC_OK;
 }
 

@@ -1,7 +1,7 @@
 """The multi-rank loss levels' host restatement (aiqmc.Loss.loss._host_level / _mean_var, what gloo
 ranks run) through the assertions of the HIP level kernels (tests/test_gpu_reductions.py): R ranks
 simulated by slicing one batch and adding the rank vectors, unequal splits included, against the
-numpy float64 restatement of the formulas in csrc/aiqmc.hip's k_lossr_* header comment.  CPU only."""
+numpy float64 restatement of the formulas in csrc/loss.hip's k_lossr_* header comment.  CPU only."""
 import numpy as np
 import pytest
 import torch

@@ -24,21 +24,6 @@ _VARIANT = os.environ.get("AIQMC_LIB_VARIANT", "")
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)),
                         "libaiqmc_hip.so" if not _VARIANT else f"libaiqmc_hip_{_VARIANT}.so")
 
-EXPORTED_SYMBOLS = (
-    "aiqmc_create", "aiqmc_destroy", "aiqmc_param_count", "aiqmc_set_params", "aiqmc_set_params_device",
-    "aiqmc_logpsi", "aiqmc_logpsi_grad", "aiqmc_local_energy", "aiqmc_local_energy_complex", "aiqmc_mc_step",
-    "aiqmc_workspace_bytes", "aiqmc_last_error", "aiqmc_supported_shapes",
-    "aiqmc_profile_enable", "aiqmc_profile_read", "aiqmc_debug_logpsi_grad_forward",
-    "aiqmc_debug_set_proposal_reuse", "aiqmc_debug_phase_cycles", "aiqmc_debug_local_energy_forward",
-    "aiqmc_set_ecp", "aiqmc_local_energy_ecp", "aiqmc_local_energy_ecp_complex", "aiqmc_logpsi_param_grad",
-    "aiqmc_dmc_drift_diffusion", "aiqmc_dmc_weights", "aiqmc_dmc_branch", "aiqmc_dmc_tmoves", "aiqmc_phase_param_grad",
-    "aiqmc_dmc_weights_ex", "aiqmc_dmc_cut_minima", "aiqmc_orbitals", "aiqmc_debug_set_ablate", "aiqmc_debug_set_fuse_accept", "aiqmc_debug_set_walker_pivots", "aiqmc_debug_set_packed_walkers", "aiqmc_debug_set_quad_pivoted", "aiqmc_debug_set_lap_waves",
-    "aiqmc_debug_set_fuse_reduce", "aiqmc_energy_stats", "aiqmc_energy_stats_final",
-    "aiqmc_debug_limdrift_factor", "aiqmc_debug_launch_lds", "aiqmc_loss_weights",
-    "aiqmc_param_grad_weighted", "aiqmc_loss_level", "aiqmc_loss_pack", "aiqmc_loss_final", "aiqmc_sr_gram",
-    "aiqmc_spin_squared", "aiqmc_dipole", "aiqmc_debug_set_obs_chunk",
-)
-
 PROF_MC_PROPOSAL = 0   # proposal value+gradient launches of aiqmc_mc_step
 PROF_MC_WALKER = 1     # walker gradient launches of aiqmc_mc_step
 PROF_LOCAL_ENERGY = 2  # aiqmc_local_energy launches
@@ -81,6 +66,73 @@ class AiqmcEcp(ctypes.Structure):
     ]
 
 
+_vp, _i32, _i64, _u64, _dbl = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64, ctypes.c_double
+_int, _str = ctypes.c_int, ctypes.c_char_p
+
+
+def _p(t):
+    return ctypes.POINTER(t)
+
+
+# The C-ABI of include/aiqmc.h, declared once: name -> (restype, argtypes); load() applies it.
+# argtypes None: the function takes no argument and ctypes' default is left alone.
+_SIGNATURES = {
+    "aiqmc_create": (_int, [_p(AiqmcCfg), _p(_vp)]),
+    "aiqmc_destroy": (_int, [_vp]),
+    "aiqmc_param_count": (_i64, [_vp]),
+    "aiqmc_workspace_bytes": (_i64, [_vp]),
+    "aiqmc_last_error": (_str, None),
+    "aiqmc_supported_shapes": (_str, None),
+    "aiqmc_set_params": (_int, [_vp, _p(_dbl), _i64, _vp]),
+    "aiqmc_set_params_device": (_int, [_vp, _vp, _i64, _vp]),
+    "aiqmc_logpsi": (_int, [_vp, _vp, _i32, _vp, _vp, _vp]),
+    "aiqmc_logpsi_grad": (_int, [_vp, _vp, _i32, _vp, _vp, _vp]),
+    "aiqmc_orbitals": (_int, [_vp, _vp, _i32, _vp, _vp, _vp, _vp]),
+    "aiqmc_local_energy": (_int, [_vp, _vp, _i32, _vp, _vp, _vp, _vp]),
+    "aiqmc_local_energy_complex": (_int, [_vp, _vp, _i32, _vp, _vp, _vp]),
+    "aiqmc_mc_step": (_int, [_vp, _vp, _i32, _i32, _dbl, _i32, _vp, _vp, _vp, _u64, _u64, _vp, _vp]),
+    "aiqmc_logpsi_param_grad": (_int, [_vp, _vp, _i32, _vp, _vp, _vp, _vp]),
+    "aiqmc_phase_param_grad": (_int, [_vp, _vp, _i32, _vp, _vp, _vp, _vp]),
+    "aiqmc_param_grad_weighted": (_int, [_vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp]),
+    "aiqmc_set_ecp": (_int, [_vp, _p(AiqmcEcp)]),
+    "aiqmc_local_energy_ecp": (_int, [_vp, _vp, _i32, _i32, _vp, _u64, _u64, _vp, _vp, _vp, _vp, _vp]),
+    "aiqmc_local_energy_ecp_complex": (_int, [_vp, _vp, _i32, _i32, _vp, _u64, _u64, _vp, _vp, _vp]),
+    "aiqmc_dmc_drift_diffusion": (_int, [_vp, _vp, _i32, _dbl, _i32, _vp, _vp, _vp, _u64, _u64, _vp, _vp, _vp, _vp]),
+    "aiqmc_dmc_weights": (_int, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _dbl, _dbl, _dbl, _dbl, _vp, _vp]),
+    "aiqmc_dmc_weights_ex": (_int, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _dbl, _vp, _vp, _dbl, _dbl, _dbl, _vp, _vp,
+                                    _vp]),
+    "aiqmc_dmc_cut_minima": (_int, [_vp, _i32, _vp, _vp, _vp, _dbl, _dbl, _vp, _vp]),
+    "aiqmc_dmc_branch": (_int, [_vp, _i32, _vp, _dbl, _vp, _vp, _vp]),
+    "aiqmc_dmc_tmoves": (_int, [_vp, _vp, _i32, _dbl, _i32, _vp, _vp, _vp, _u64, _u64, _vp, _vp]),
+    "aiqmc_spin_squared": (_int, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "aiqmc_dipole": (_int, [_vp, _vp, _i32, _vp, _vp]),
+    "aiqmc_profile_enable": (_int, [_vp, _i32]),
+    "aiqmc_profile_read": (_int, [_vp, _i32, _p(_dbl), _p(_i64)]),
+    "aiqmc_energy_stats": (_int, [_vp, _i32, _i64, _vp, _i32, _vp]),
+    "aiqmc_energy_stats_final": (_int, [_vp, _vp]),
+    "aiqmc_loss_weights": (_int, [_vp, _vp, _i32, _i64, _dbl, _i32, _dbl, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "aiqmc_loss_level": (_int, [_i32, _vp, _vp, _i32, _i64, _vp, _vp, _dbl, _dbl, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "aiqmc_loss_pack": (_int, [_vp, _vp, _vp, _i32, _i32, _vp, _vp]),
+    "aiqmc_loss_final": (_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "aiqmc_sr_gram": (_int, [_vp, _vp, _i32, _i64, _i32, _vp, _vp, _vp, _i32, _vp]),
+    "aiqmc_debug_logpsi_grad_forward": (_int, [_vp, _vp, _i32, _vp, _vp, _vp]),
+    "aiqmc_debug_local_energy_forward": (_int, [_vp, _vp, _i32, _vp, _vp, _vp, _vp]),
+    "aiqmc_debug_limdrift_factor": (_int, [_vp, _vp, _i32, _dbl, _i32, _p(_dbl), _vp]),
+    "aiqmc_debug_launch_lds": (_int, [_i32, _i32, _i32, _i32, _p(_i32), _p(_i32)]),
+    "aiqmc_debug_phase_cycles": (_int, [_vp, _vp]),
+    "aiqmc_debug_set_ablate": (_int, [_vp, _i32]),
+    "aiqmc_debug_set_fuse_accept": (_int, [_vp, _i32]),
+    "aiqmc_debug_set_walker_pivots": (_int, [_vp, _i32]),
+    "aiqmc_debug_set_packed_walkers": (_int, [_vp, _i32]),
+    "aiqmc_debug_set_quad_pivoted": (_int, [_vp, _i32]),
+    "aiqmc_debug_set_fuse_reduce": (_int, [_vp, _i32]),
+    "aiqmc_debug_set_lap_waves": (_int, [_vp, _i32]),
+    "aiqmc_debug_set_proposal_reuse": (_int, [_vp, _i32]),
+    "aiqmc_debug_set_obs_chunk": (_int, [_vp, _i32]),
+}
+EXPORTED_SYMBOLS = tuple(_SIGNATURES)
+
+
 _lib: Optional[ctypes.CDLL] = None
 
 
@@ -109,93 +161,11 @@ def load() -> ctypes.CDLL:
             f"{LIB_PATH} not found: build it with `make -C <pkg>/csrc` or __graft_entry__.build(); "
             "the AIQMC hot path has no CPU fallback")
     lib = ctypes.CDLL(LIB_PATH)
-    vp, i32, i64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
-    lib.aiqmc_create.argtypes = [ctypes.POINTER(AiqmcCfg), ctypes.POINTER(vp)]
-    lib.aiqmc_destroy.argtypes = [vp]
-    lib.aiqmc_param_count.argtypes = [vp]
-    lib.aiqmc_param_count.restype = i64
-    lib.aiqmc_workspace_bytes.argtypes = [vp]
-    lib.aiqmc_workspace_bytes.restype = i64
-    lib.aiqmc_set_params.argtypes = [vp, ctypes.POINTER(ctypes.c_double), i64, vp]
-    lib.aiqmc_set_params_device.argtypes = [vp, vp, i64, vp]
-    lib.aiqmc_logpsi.argtypes = [vp, vp, i32, vp, vp, vp]
-    lib.aiqmc_logpsi_grad.argtypes = [vp, vp, i32, vp, vp, vp]
-    lib.aiqmc_orbitals.argtypes = [vp, vp, i32, vp, vp, vp, vp]
-    lib.aiqmc_local_energy.argtypes = [vp, vp, i32, vp, vp, vp, vp]
-    lib.aiqmc_local_energy_complex.argtypes = [vp, vp, i32, vp, vp, vp]
-    lib.aiqmc_mc_step.argtypes = [vp, vp, i32, i32, ctypes.c_double, i32, vp, vp, vp,
-                                  ctypes.c_uint64, ctypes.c_uint64, vp, vp]
-    lib.aiqmc_debug_logpsi_grad_forward.argtypes = [vp, vp, i32, vp, vp, vp]
-    lib.aiqmc_debug_logpsi_grad_forward.restype = ctypes.c_int
-    lib.aiqmc_debug_local_energy_forward.argtypes = [vp, vp, i32, vp, vp, vp, vp]
-    lib.aiqmc_debug_local_energy_forward.restype = ctypes.c_int
-    lib.aiqmc_debug_set_ablate.argtypes = [vp, i32]
-    lib.aiqmc_debug_set_ablate.restype = ctypes.c_int
-    lib.aiqmc_debug_set_fuse_accept.argtypes = [vp, i32]
-    lib.aiqmc_debug_set_fuse_accept.restype = ctypes.c_int
-    lib.aiqmc_loss_weights.argtypes = [vp, vp, i32, i64, ctypes.c_double, i32, ctypes.c_double, vp, vp, vp, vp, vp,
-                                       vp]
-    lib.aiqmc_loss_weights.restype = ctypes.c_int
-    lib.aiqmc_debug_launch_lds.argtypes = [i32, i32, i32, i32, ctypes.POINTER(i32), ctypes.POINTER(i32)]
-    lib.aiqmc_debug_launch_lds.restype = ctypes.c_int
-    lib.aiqmc_debug_set_walker_pivots.argtypes = [vp, i32]
-    lib.aiqmc_debug_set_walker_pivots.restype = ctypes.c_int
-    lib.aiqmc_debug_set_packed_walkers.argtypes = [vp, i32]
-    lib.aiqmc_debug_set_packed_walkers.restype = ctypes.c_int
-    lib.aiqmc_debug_set_quad_pivoted.argtypes = [vp, i32]
-    lib.aiqmc_debug_set_quad_pivoted.restype = ctypes.c_int
-    lib.aiqmc_debug_set_fuse_reduce.argtypes = [vp, i32]
-    lib.aiqmc_debug_set_fuse_reduce.restype = ctypes.c_int
-    lib.aiqmc_debug_limdrift_factor.argtypes = [vp, vp, i32, ctypes.c_double, i32,
-                                                ctypes.POINTER(ctypes.c_double), vp]
-    lib.aiqmc_debug_limdrift_factor.restype = ctypes.c_int
-    lib.aiqmc_debug_set_lap_waves.argtypes = [vp, i32]
-    lib.aiqmc_debug_set_lap_waves.restype = ctypes.c_int
-    lib.aiqmc_debug_set_proposal_reuse.argtypes = [vp, i32]
-    lib.aiqmc_debug_set_proposal_reuse.restype = ctypes.c_int
-    lib.aiqmc_debug_phase_cycles.argtypes = [vp, vp]
-    lib.aiqmc_debug_phase_cycles.restype = ctypes.c_int
-    lib.aiqmc_logpsi_param_grad.argtypes = [vp, vp, i32, vp, vp, vp, vp]
-    lib.aiqmc_phase_param_grad.argtypes = [vp, vp, i32, vp, vp, vp, vp]
-    dbl, u64 = ctypes.c_double, ctypes.c_uint64
-    lib.aiqmc_dmc_drift_diffusion.argtypes = [vp, vp, i32, dbl, i32, vp, vp, vp, u64, u64, vp, vp, vp, vp]
-    lib.aiqmc_dmc_weights.argtypes = [vp, i32, vp, vp, vp, vp, vp, dbl, dbl, dbl, dbl, vp, vp]
-    lib.aiqmc_dmc_weights_ex.argtypes = [vp, i32, vp, vp, vp, vp, vp, dbl, vp, vp, dbl, dbl, dbl, vp, vp, vp]
-    lib.aiqmc_dmc_cut_minima.argtypes = [vp, i32, vp, vp, vp, dbl, dbl, vp, vp]
-    lib.aiqmc_dmc_branch.argtypes = [vp, i32, vp, dbl, vp, vp, vp]
-    lib.aiqmc_dmc_tmoves.argtypes = [vp, vp, i32, dbl, i32, vp, vp, vp, u64, u64, vp, vp]
-    lib.aiqmc_set_ecp.argtypes = [vp, ctypes.POINTER(AiqmcEcp)]
-    lib.aiqmc_local_energy_ecp.argtypes = [vp, vp, i32, i32, vp, ctypes.c_uint64, ctypes.c_uint64, vp, vp, vp,
-                                           vp, vp]
-    lib.aiqmc_local_energy_ecp_complex.argtypes = [vp, vp, i32, i32, vp, ctypes.c_uint64, ctypes.c_uint64, vp, vp,
-                                                   vp]
-    lib.aiqmc_profile_enable.argtypes = [vp, i32]
-    lib.aiqmc_profile_read.argtypes = [vp, i32, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(i64)]
-    lib.aiqmc_energy_stats.argtypes = [vp, i32, i64, vp, i32, vp]
-    lib.aiqmc_energy_stats_final.argtypes = [vp, vp]
-    lib.aiqmc_param_grad_weighted.argtypes = [vp, vp, i32, i32, vp, i32, vp, vp, vp]
-    lib.aiqmc_loss_level.argtypes = [i32, vp, vp, i32, i64, vp, vp, dbl, dbl, i32, vp, vp, vp, vp, vp, vp]
-    lib.aiqmc_loss_pack.argtypes = [vp, vp, vp, i32, i32, vp, vp]
-    lib.aiqmc_loss_final.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]
-    lib.aiqmc_sr_gram.argtypes = [vp, vp, i32, i64, i32, vp, vp, vp, i32, vp]
-    lib.aiqmc_sr_gram.restype = ctypes.c_int
-    lib.aiqmc_spin_squared.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp]
-    lib.aiqmc_spin_squared.restype = ctypes.c_int
-    lib.aiqmc_dipole.argtypes = [vp, vp, i32, vp, vp]
-    lib.aiqmc_dipole.restype = ctypes.c_int
-    lib.aiqmc_debug_set_obs_chunk.argtypes = [vp, i32]
-    lib.aiqmc_debug_set_obs_chunk.restype = ctypes.c_int
-    lib.aiqmc_last_error.restype = ctypes.c_char_p
-    lib.aiqmc_supported_shapes.restype = ctypes.c_char_p
-    for name in ("aiqmc_create", "aiqmc_destroy", "aiqmc_set_params", "aiqmc_set_params_device", "aiqmc_logpsi",
-                 "aiqmc_logpsi_grad", "aiqmc_local_energy", "aiqmc_local_energy_complex", "aiqmc_mc_step", "aiqmc_profile_enable",
-                 "aiqmc_profile_read", "aiqmc_set_ecp", "aiqmc_local_energy_ecp", "aiqmc_local_energy_ecp_complex",
-                 "aiqmc_logpsi_param_grad",
-                 "aiqmc_dmc_drift_diffusion", "aiqmc_dmc_weights", "aiqmc_dmc_branch", "aiqmc_dmc_tmoves",
-                 "aiqmc_phase_param_grad", "aiqmc_dmc_weights_ex", "aiqmc_dmc_cut_minima", "aiqmc_orbitals",
-                 "aiqmc_energy_stats", "aiqmc_energy_stats_final", "aiqmc_param_grad_weighted",
-                 "aiqmc_loss_level", "aiqmc_loss_pack", "aiqmc_loss_final"):
-        getattr(lib, name).restype = ctypes.c_int
+    for name, (restype, argtypes) in _SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype = restype
+        if argtypes is not None:
+            fn.argtypes = argtypes
     _lib = lib
     return lib
 

@@ -306,12 +306,11 @@ extern "C" {
 int aiqmc_energy_stats(const void* e_l, int32_t dtype, int64_t n, double* out, int32_t finalize, void* stream) {
   if (n <= 0) return fail(AIQMC_EINVAL, "empty batch");
   if (!e_l || !out) return fail(AIQMC_EINVAL, "null argument");
-  if (dtype != AIQMC_F32 && dtype != AIQMC_F64) return fail(AIQMC_EINVAL, "dtype must be AIQMC_F32 or AIQMC_F64");
-  hipStream_t s = (hipStream_t)stream;
-  if (dtype == AIQMC_F32)
-    k_energy_stats<float><<<dim3(1), dim3(1024), 0, s>>>((const float*)e_l, n, out, finalize != 0);
-  else
-    k_energy_stats<double><<<dim3(1), dim3(1024), 0, s>>>((const double*)e_l, n, out, finalize != 0);
+  if (!is_dtype(dtype)) return fail(AIQMC_EINVAL, "dtype must be AIQMC_F32 or AIQMC_F64");
+  by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    k_energy_stats<T><<<dim3(1), dim3(1024), 0, (hipStream_t)stream>>>((const T*)e_l, n, out, finalize != 0);
+  });
   HIPCHK(hipGetLastError());
   return AIQMC_OK;
 }
@@ -321,16 +320,13 @@ int aiqmc_loss_weights(const void* e_re, const void* e_im, int32_t dtype, int64_
                        void* clipped_im, double* stats, void* stream) {
   if (n <= 0) return fail(AIQMC_EINVAL, "empty batch");
   if (!e_re || !w_re || !stats) return fail(AIQMC_EINVAL, "null argument");
-  if (dtype != AIQMC_F32 && dtype != AIQMC_F64) return fail(AIQMC_EINVAL, "dtype must be AIQMC_F32 or AIQMC_F64");
-  hipStream_t s = (hipStream_t)stream;
-  if (dtype == AIQMC_F32)
-    k_loss_weights<float><<<dim3(1), dim3(1024), 0, s>>>((const float*)e_re, (const float*)e_im, n, clip_scale,
-                                                         center_at_clipped, wscale, (float*)w_re, (float*)w_im,
-                                                         (float*)clipped_re, (float*)clipped_im, stats);
-  else
-    k_loss_weights<double><<<dim3(1), dim3(1024), 0, s>>>((const double*)e_re, (const double*)e_im, n, clip_scale,
-                                                          center_at_clipped, wscale, (double*)w_re, (double*)w_im,
-                                                          (double*)clipped_re, (double*)clipped_im, stats);
+  if (!is_dtype(dtype)) return fail(AIQMC_EINVAL, "dtype must be AIQMC_F32 or AIQMC_F64");
+  by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    k_loss_weights<T><<<dim3(1), dim3(1024), 0, (hipStream_t)stream>>>(
+        (const T*)e_re, (const T*)e_im, n, clip_scale, center_at_clipped, wscale, (T*)w_re, (T*)w_im, (T*)clipped_re,
+        (T*)clipped_im, stats);
+  });
   HIPCHK(hipGetLastError());
   return AIQMC_OK;
 }
@@ -347,29 +343,24 @@ int aiqmc_loss_level(int32_t level, const void* e_re, const void* e_im, int32_t 
                      void* wp, void* clipped_re, void* clipped_im, double* out, void* stream) {
   if (n <= 0) return fail(AIQMC_EINVAL, "empty batch");
   if (!e_re || !out) return fail(AIQMC_EINVAL, "null argument");
-  if (dtype != AIQMC_F32 && dtype != AIQMC_F64) return fail(AIQMC_EINVAL, "dtype must be AIQMC_F32 or AIQMC_F64");
-  hipStream_t s = (hipStream_t)stream;
-  const bool f32 = dtype == AIQMC_F32;
-  if (level == 1) {
-    if (f32) k_lossr_l1<float><<<dim3(1), dim3(1024), 0, s>>>((const float*)e_re, (const float*)e_im, n, out);
-    else k_lossr_l1<double><<<dim3(1), dim3(1024), 0, s>>>((const double*)e_re, (const double*)e_im, n, out);
-  } else if (level == 2) {
-    if (!L1) return fail(AIQMC_EINVAL, "level 2 needs the summed level-1 vector");
-    if (f32) k_lossr_l2<float><<<dim3(1), dim3(1024), 0, s>>>((const float*)e_re, (const float*)e_im, n, L1, out);
-    else k_lossr_l2<double><<<dim3(1), dim3(1024), 0, s>>>((const double*)e_re, (const double*)e_im, n, L1, out);
-  } else if (level == 3) {
-    if (!L1 || !w || (clip_scale > 0.0 && !L2)) return fail(AIQMC_EINVAL, "level 3 needs L1, L2 (clipping) and w");
-    if (f32)
-      k_lossr_l3<float><<<dim3(1), dim3(1024), 0, s>>>((const float*)e_re, (const float*)e_im, n, L1, L2, clip_scale,
-                                                       wscale, g0, (float*)w, (float*)wp, (float*)clipped_re,
-                                                       (float*)clipped_im, out);
+  if (!is_dtype(dtype)) return fail(AIQMC_EINVAL, "dtype must be AIQMC_F32 or AIQMC_F64");
+  if (level == 2 && !L1) return fail(AIQMC_EINVAL, "level 2 needs the summed level-1 vector");
+  if (level == 3 && (!L1 || !w || (clip_scale > 0.0 && !L2)))
+    return fail(AIQMC_EINVAL, "level 3 needs L1, L2 (clipping) and w");
+  if (level < 1 || level > 3) return fail(AIQMC_EINVAL, "level must be 1, 2 or 3");
+  by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    const dim3 one(1), wg(1024);
+    hipStream_t s = (hipStream_t)stream;
+    const T *er = (const T*)e_re, *ei = (const T*)e_im;
+    if (level == 1)
+      k_lossr_l1<T><<<one, wg, 0, s>>>(er, ei, n, out);
+    else if (level == 2)
+      k_lossr_l2<T><<<one, wg, 0, s>>>(er, ei, n, L1, out);
     else
-      k_lossr_l3<double><<<dim3(1), dim3(1024), 0, s>>>((const double*)e_re, (const double*)e_im, n, L1, L2,
-                                                        clip_scale, wscale, g0, (double*)w, (double*)wp,
-                                                        (double*)clipped_re, (double*)clipped_im, out);
-  } else {
-    return fail(AIQMC_EINVAL, "level must be 1, 2 or 3");
-  }
+      k_lossr_l3<T><<<one, wg, 0, s>>>(er, ei, n, L1, L2, clip_scale, wscale, g0, (T*)w, (T*)wp, (T*)clipped_re,
+                                       (T*)clipped_im, out);
+  });
   HIPCHK(hipGetLastError());
   return AIQMC_OK;
 }
@@ -377,14 +368,12 @@ int aiqmc_loss_level(int32_t level, const void* e_re, const void* e_im, int32_t 
 int aiqmc_loss_pack(const void* g, const void* gp, const void* g0, int32_t dtype, int32_t P, double* L3,
                     void* stream) {
   if (!g || !L3 || P <= 0) return fail(AIQMC_EINVAL, "null argument");
-  hipStream_t s = (hipStream_t)stream;
-  const dim3 gr((P + 255) / 256);
-  if (dtype == AIQMC_F32)
-    k_lossr_pack<float><<<gr, dim3(256), 0, s>>>((const float*)g, (const float*)gp, (const float*)g0, P, L3);
-  else if (dtype == AIQMC_F64)
-    k_lossr_pack<double><<<gr, dim3(256), 0, s>>>((const double*)g, (const double*)gp, (const double*)g0, P, L3);
-  else
-    return fail(AIQMC_EINVAL, "dtype must be AIQMC_F32 or AIQMC_F64");
+  if (!is_dtype(dtype)) return fail(AIQMC_EINVAL, "dtype must be AIQMC_F32 or AIQMC_F64");
+  by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    k_lossr_pack<T><<<blocks(P, 256), dim3(256), 0, (hipStream_t)stream>>>((const T*)g, (const T*)gp, (const T*)g0, P,
+                                                                          L3);
+  });
   HIPCHK(hipGetLastError());
   return AIQMC_OK;
 }
@@ -392,15 +381,13 @@ int aiqmc_loss_pack(const void* g, const void* gp, const void* g0, int32_t dtype
 int aiqmc_loss_final(const double* L1, const double* L3, int32_t P, int32_t g0, int32_t center_at_clipped,
                      int32_t world, int32_t dtype, void* grad, double* stats, void* stream) {
   if (!L1 || !L3 || !grad || !stats || P <= 0 || world <= 0) return fail(AIQMC_EINVAL, "null argument");
-  hipStream_t s = (hipStream_t)stream;
-  const dim3 gr((P + 255) / 256);
+  if (!is_dtype(dtype)) return fail(AIQMC_EINVAL, "dtype must be AIQMC_F32 or AIQMC_F64");
   const double iw = 1.0 / (double)world;
-  if (dtype == AIQMC_F32)
-    k_lossr_final<float><<<gr, dim3(256), 0, s>>>(L1, L3, P, g0, center_at_clipped, iw, (float*)grad, stats);
-  else if (dtype == AIQMC_F64)
-    k_lossr_final<double><<<gr, dim3(256), 0, s>>>(L1, L3, P, g0, center_at_clipped, iw, (double*)grad, stats);
-  else
-    return fail(AIQMC_EINVAL, "dtype must be AIQMC_F32 or AIQMC_F64");
+  by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    k_lossr_final<T><<<blocks(P, 256), dim3(256), 0, (hipStream_t)stream>>>(L1, L3, P, g0, center_at_clipped, iw,
+                                                                           (T*)grad, stats);
+  });
   HIPCHK(hipGetLastError());
   return AIQMC_OK;
 }

@@ -156,35 +156,19 @@ int aiqmc_spin_squared(aiqmc_ctx* c, const void* pos, int32_t B, void* s2_re, vo
   int G = 4;
   while (G < K) G *= 2;
   hipStream_t s = (hipStream_t)stream;
-  const bool f32 = c->dtype == AIQMC_F32;
-  const int* rowsrc = c->d_rowsrc.as<int>();
   void *lp = c->d_obs_lp.as(), *ph = c->d_obs_ph.as();
   for (int b0 = 0; b0 < B; b0 += W) {
     const int nw = B - b0 < W ? B - b0 : W;
     const int nconf = nw * (K + 1);
-    const unsigned nbx = (unsigned)(((int64_t)nconf * c->N + 255) / 256);
-    if (f32)
-      k_s2_exchange<float><<<dim3(nbx), dim3(256), 0, s>>>((const float*)pos, rowsrc, c->N, c->nup, c->ndn, b0, nconf,
-                                                           c->d_obs_x.as<float>());
-    else
-      k_s2_exchange<double><<<dim3(nbx), dim3(256), 0, s>>>((const double*)pos, rowsrc, c->N, c->nup, c->ndn, b0,
-                                                            nconf, c->d_obs_x.as<double>());
-    // the arguments of aiqmc_logpsi
-    KArgs ka;
-    std::memset(&ka, 0, sizeof(ka));
-    ka.nup = c->nup;
-    ka.rowsrc = rowsrc;
-    ka.prm = c->d_prm.as();
-    ka.one_wave = c->packed_walkers ? 0 : 1;
-    ka.quad_pivoted = c->quad_pivoted;
-    ka.nconf = nconf;
-    ka.pos = c->d_obs_x.as();
-    ka.logabs = lp;
+    KArgs ka = walker_args(c, c->d_obs_x.as(), nconf, lp, c->d_obs_wc);   // the arguments of aiqmc_logpsi
     ka.phase = ph;
-    ka.wcache = c->d_obs_wc.as();
-    ops.walker(c->dtype, MODE_GRAD, ka, nconf, s);
-    if (f32) s2_reduce_launch<float>(G, nw, lp, ph, K, b0, diag, s2_re, s2_im, dlogabs, dphase, s);
-    else s2_reduce_launch<double>(G, nw, lp, ph, K, b0, diag, s2_re, s2_im, dlogabs, dphase, s);
+    by_dtype(c->dtype, [&](auto t) {
+      using T = decltype(t);
+      k_s2_exchange<T><<<blocks((int64_t)nconf * c->N, 256), dim3(256), 0, s>>>(
+          (const T*)pos, c->d_rowsrc.as<int>(), c->N, c->nup, c->ndn, b0, nconf, c->d_obs_x.as<T>());
+      ops.walker(c->dtype, MODE_GRAD, ka, nconf, s);
+      s2_reduce_launch<T>(G, nw, lp, ph, K, b0, diag, s2_re, s2_im, dlogabs, dphase, s);
+    });
   }
   HIPCHK(hipGetLastError());
   return AIQMC_OK;
@@ -201,11 +185,10 @@ int aiqmc_dipole(aiqmc_ctx* c, const void* pos, int32_t B, void* mu, void* strea
   for (int a = 0; a < c->A; ++a)
     for (int d = 0; d < 3; ++d) nuc[d] += c->charges[a] * c->atoms[3 * a + d];
   hipStream_t s = (hipStream_t)stream;
-  const unsigned nbx = (unsigned)(((int64_t)B * 3 + 255) / 256);
-  if (c->dtype == AIQMC_F32)
-    k_dipole<float><<<dim3(nbx), dim3(256), 0, s>>>((const float*)pos, c->N, B, nuc[0], nuc[1], nuc[2], (float*)mu);
-  else
-    k_dipole<double><<<dim3(nbx), dim3(256), 0, s>>>((const double*)pos, c->N, B, nuc[0], nuc[1], nuc[2], (double*)mu);
+  by_dtype(c->dtype, [&](auto t) {
+    using T = decltype(t);
+    k_dipole<T><<<blocks((int64_t)B * 3, 256), dim3(256), 0, s>>>((const T*)pos, c->N, B, nuc[0], nuc[1], nuc[2], (T*)mu);
+  });
   HIPCHK(hipGetLastError());
   return AIQMC_OK;
 }

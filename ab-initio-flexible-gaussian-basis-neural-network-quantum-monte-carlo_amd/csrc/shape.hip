@@ -232,28 +232,30 @@ static void gmap_impl(const aiqmc_ctx* c, std::vector<int>& map) {
   for (int k = 0; k < NYW * N; ++k) put(-2 - k);
 }
 
-template <int N, int A>
-static int set_lds_impl() {
-  const int sizes[6] = {Smem<float, N, false>::bytes,  Smem<float, N, true>::bytes,  Smem<double, N, false>::bytes,
-                        Smem<double, N, true>::bytes,  SmemRev<float, N, A>::bytes, SmemRev<double, N, A>::bytes};
-  const void* fns[6] = {(const void*)&k_walker<float, N, A, MODE_GRAD>,  (const void*)&k_walker<float, N, A, MODE_LAP>,
-                        (const void*)&k_walker<double, N, A, MODE_GRAD>, (const void*)&k_walker<double, N, A, MODE_LAP>,
-                        (const void*)&k_walker_rev<float, N, A>,         (const void*)&k_walker_rev<double, N, A>};
-  for (int k = 0; k < 6; ++k) {
-    if (sizes[k] > 65536) {
-      hipError_t e = hipFuncSetAttribute(fns[k], hipFuncAttributeMaxDynamicSharedMemorySize, sizes[k]);
-      if (e != hipSuccess) return fail(AIQMC_EHIP, std::string("hipFuncSetAttribute: ") + hipGetErrorString(e));
-    }
-  }
-  {   // proposal launches: RevWpb configurations per workgroup
-    const int pb = RevWpb<float, true>::value * SmemRev<float, N, A, kFwdReg>::bytes;
-    if (pb > 65536) {
-      hipError_t e = hipFuncSetAttribute((const void*)&k_walker_rev<float, N, A, false, true>,
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, pb);
-      if (e != hipSuccess) return fail(AIQMC_EHIP, std::string("hipFuncSetAttribute: ") + hipGetErrorString(e));
-    }
-  }
+// hipFuncSetAttribute for a launch that takes more dynamic LDS than the default 64 KB limit
+static int raise_lds(const void* fn, int bytes) {
+  if (bytes <= 65536) return 0;
+  hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  if (e != hipSuccess) return fail(AIQMC_EHIP, std::string("hipFuncSetAttribute: ") + hipGetErrorString(e));
   return 0;
+}
+
+template <typename T, int N, int A>
+static int set_lds_t() {
+  if (int rc = raise_lds((const void*)&k_walker<T, N, A, MODE_GRAD>, Smem<T, N, false>::bytes)) return rc;
+  if (int rc = raise_lds((const void*)&k_walker<T, N, A, MODE_LAP>, Smem<T, N, true>::bytes)) return rc;
+  if (int rc = raise_lds((const void*)&k_walker_rev<T, N, A>, SmemRev<T, N, A>::bytes)) return rc;
+  // proposal launches: RevWpb configurations per workgroup.  fp32 only: an fp64 proposal workgroup
+  // holds one configuration, within the default limit for every shape
+  constexpr int pb = RevWpb<T, true>::value * SmemRev<T, N, A, kFwdReg>::bytes;
+  if constexpr (sizeof(T) == 4) return raise_lds((const void*)&k_walker_rev<T, N, A, false, true>, pb);
+  else static_assert(pb <= 65536, "fp64 proposal launches need the raised LDS limit too");
+  return 0;
+}
+template <int N, int A>
+static int set_lds_impl() {   // both dtypes: the attribute belongs to the kernel, not to a context
+  if (int rc = set_lds_t<float, N, A>()) return rc;
+  return set_lds_t<double, N, A>();
 }
 
 // MODE_GRAD -> reverse-mode value+gradient kernel (walker_rev.h); MODE_LAP -> forward
@@ -332,50 +334,63 @@ static bool use_pw7(int nconf) {
 }
 #endif
 
+// Which kernel a walker launch reaches (ops.walker): the first row that matches, from the top.
+// The launch kind is not named, it is read off the KArgs fields.  T = the dtype; n = nconf;
+// Wp = RevWpb<T, true>, Ww = RevWpb<T, false> configurations per workgroup (both 1 for fp64);
+// NSL = QSlot<N>::NSL configurations per wave; LDS = dynamic LDS bytes.
+//
+//  #  mode      conditions                                          kernel                      grid                block  LDS
+//  1  GRAD      N <= 8, proposal, ecache, value_only, !orb          k_quad_value<T>             prop_blocks(n,NSL)  64     0
+//  2  GRAD      N <= 8, proposal, ecache, !value_only, !orb,        k_quad_grad<T>              ceil(n / NSL)       64     0
+//               !ablate, not (N > 4 and AIQMC_QUAD_GRAD=0)
+//  3  GRAD      N <= 8, !proposal, wcache, !value_only, !orb,       k_quad_grad<T, walker>      ceil(n / NSL)       64     0
+//               !lapcache, !one_wave
+//  4  LAP       --                                                  k_walker<T, MODE_LAP>       n                   64     Smem<T, N, true>
+//  5  GRAD      proposal, ecache, fp32, (N, A) = (14, 2), a         k_walker_rev<PROP, PW7>     prop_blocks(n, Wp)  64 Wp  Wp SmemRev<kFwdReg, PW7>
+//               -DAQ_PW7 build, use_pw7(n)
+//  6  GRAD      proposal, ecache                                    k_walker_rev<T, PROP>       prop_blocks(n, Wp)  64 Wp  Wp SmemRev<T, kFwdReg>
+//  7  GRAD      fp32, walk_split, !proposal, !value_only,           k_walker_rev<float, SPL>    n                   128    SmemRev<float>
+//               not AIQMC_WALK_SPLIT=0
+//  8  GRAD      --                                                  k_walker_rev<T>             ceil(n / Ww)        64 Ww  Ww SmemRev<T>
+//  9  GRAD_FWD  --                                                  k_walker<T, MODE_GRAD>      n                   64     Smem<T, N, false>
+//
+// So proposals without an ecache (proposal reuse off) and value_only / orb walker launches take row
+// 8.  Rows 5 and 7 are instantiated for float alone; every other row for both dtypes.
+template <typename T, int N, int A>
+static void walker_launch(int mode, const KArgs& ka, int nconf, hipStream_t s) {
+  if (mode == MODE_GRAD && quad_small<T, N, A>(ka, nconf, s)) return;
+  if (mode == MODE_LAP) {
+    k_walker<T, N, A, MODE_LAP><<<dim3(nconf), dim3(64), Smem<T, N, true>::bytes, s>>>(ka);
+  } else if (mode == MODE_GRAD && ka.proposal && ka.ecache) {   // proposals from the walker cache
+    constexpr int W = RevWpb<T, true>::value;
+#ifdef AQ_PW7
+    if constexpr (sizeof(T) == 4 && N == 14 && A == 2) {
+      if (use_pw7(nconf)) {
+        k_walker_rev<T, N, A, false, true, true><<<dim3(prop_blocks(nconf, W)), dim3(64 * W),
+                                                  W * SmemRev<T, N, A, kFwdReg, true>::bytes, s>>>(ka);
+        return;
+      }
+    }
+#endif
+    k_walker_rev<T, N, A, false, true><<<dim3(prop_blocks(nconf, W)), dim3(64 * W),
+                                        W * SmemRev<T, N, A, kFwdReg>::bytes, s>>>(ka);
+  } else if (mode == MODE_GRAD) {
+    if constexpr (sizeof(T) == 4) {   // two waves per walker: an fp32 instantiation only
+      if (ka.walk_split && !ka.proposal && !ka.value_only && walk_split_on()) {
+        k_walker_rev<T, N, A, false, false, false, false, true><<<dim3(nconf), dim3(128), SmemRev<T, N, A>::bytes, s>>>(ka);
+        return;
+      }
+    }
+    constexpr int W = RevWpb<T, false>::value;
+    static_assert(sizeof(T) == 4 || W == 1, "fp64 walker launches: one walker per workgroup, grid = nconf");
+    k_walker_rev<T, N, A><<<dim3((nconf + W - 1) / W), dim3(64 * W), W * SmemRev<T, N, A>::bytes, s>>>(ka);
+  } else {
+    k_walker<T, N, A, MODE_GRAD><<<dim3(nconf), dim3(64), Smem<T, N, false>::bytes, s>>>(ka);
+  }
+}
 template <int N, int A>
 static void walker_impl(int dtype, int mode, const KArgs& ka, int nconf, hipStream_t s) {
-  if (mode == MODE_GRAD && (dtype == AIQMC_F32 ? quad_small<float, N, A>(ka, nconf, s) : quad_small<double, N, A>(ka, nconf, s)))
-    return;
-  if (dtype == AIQMC_F32) {
-    if (mode == MODE_LAP)
-      k_walker<float, N, A, MODE_LAP><<<dim3(nconf), dim3(64), Smem<float, N, true>::bytes, s>>>(ka);
-    else if (mode == MODE_GRAD && ka.proposal && ka.ecache) {   // proposals from the walker cache
-#ifdef AQ_PW7
-      if constexpr (N == 14 && A == 2) {
-        if (use_pw7(nconf)) {
-          k_walker_rev<float, N, A, false, true, true><<<dim3(prop_blocks(nconf, RevWpb<float, true>::value)),
-                                                        dim3(64 * RevWpb<float, true>::value),
-                                                        RevWpb<float, true>::value * SmemRev<float, N, A, kFwdReg, true>::bytes,
-                                                        s>>>(ka);
-          return;
-        }
-      }
-#endif
-      k_walker_rev<float, N, A, false, true><<<dim3(prop_blocks(nconf, RevWpb<float, true>::value)),
-                                              dim3(64 * RevWpb<float, true>::value),
-                                              RevWpb<float, true>::value * SmemRev<float, N, A, kFwdReg>::bytes, s>>>(ka);
-    }
-    else if (mode == MODE_GRAD && ka.walk_split && !ka.proposal && !ka.value_only && walk_split_on())
-      k_walker_rev<float, N, A, false, false, false, false, true><<<dim3(nconf), dim3(128), SmemRev<float, N, A>::bytes,
-                                                                  s>>>(ka);
-    else if (mode == MODE_GRAD)
-      k_walker_rev<float, N, A><<<dim3((nconf + RevWpb<float, false>::value - 1) / RevWpb<float, false>::value),
-                                  dim3(64 * RevWpb<float, false>::value),
-                                  RevWpb<float, false>::value * SmemRev<float, N, A>::bytes, s>>>(ka);
-    else
-      k_walker<float, N, A, MODE_GRAD><<<dim3(nconf), dim3(64), Smem<float, N, false>::bytes, s>>>(ka);
-  } else {
-    if (mode == MODE_LAP)
-      k_walker<double, N, A, MODE_LAP><<<dim3(nconf), dim3(64), Smem<double, N, true>::bytes, s>>>(ka);
-    else if (mode == MODE_GRAD && ka.proposal && ka.ecache)   // proposals from the walker cache
-      k_walker_rev<double, N, A, false, true><<<dim3(prop_blocks(nconf, RevWpb<double, true>::value)),
-                                              dim3(64 * RevWpb<double, true>::value),
-                                              RevWpb<double, true>::value * SmemRev<double, N, A, kFwdReg>::bytes, s>>>(ka);
-    else if (mode == MODE_GRAD)
-      k_walker_rev<double, N, A><<<dim3(nconf), dim3(64), SmemRev<double, N, A>::bytes, s>>>(ka);
-    else
-      k_walker<double, N, A, MODE_GRAD><<<dim3(nconf), dim3(64), Smem<double, N, false>::bytes, s>>>(ka);
-  }
+  by_dtype(dtype, [&](auto t) { walker_launch<decltype(t), N, A>(mode, ka, nconf, s); });
 }
 
 // Local energy: adjoint pass (k_walker_rev<PREP>) then first-derivative pass (k_walker_lap).
@@ -391,63 +406,59 @@ static void lap_launch(const KArgs& k1, const KArgs& k2, int nconf, int waves, h
 }
 template <int N, int A>
 static void lap_impl(int dtype, const KArgs& k1, const KArgs& k2, int nconf, int waves, int phase, hipStream_t s) {
-  if (dtype == AIQMC_F32) {
-    if (phase) lap_launch<float, N, A, true>(k1, k2, nconf, waves, s);
-    else lap_launch<float, N, A, false>(k1, k2, nconf, waves, s);
-  } else {
-    if (phase) lap_launch<double, N, A, true>(k1, k2, nconf, waves, s);
-    else lap_launch<double, N, A, false>(k1, k2, nconf, waves, s);
-  }
+  by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    if (phase) lap_launch<T, N, A, true>(k1, k2, nconf, waves, s);
+    else lap_launch<T, N, A, false>(k1, k2, nconf, waves, s);
+  });
 }
 
 template <int N, int A>
 static void moved_impl(int dtype, const KArgs& ka, hipStream_t s) {
-  if (ka.value_only && ka.xnew) {   // pp quadrature: values only, one configuration per lane
-    const int nv = (ka.nconf + 63) / 64;
-    if (dtype == AIQMC_F32)
-      k_moved_value<float, N, A><<<dim3(prop_blocks(nv, MOVED_WPB)), dim3(64 * MOVED_WPB), 0, s>>>(ka);
-    else
-      k_moved_value<double, N, A><<<dim3(prop_blocks(nv, MOVED_WPB)), dim3(64 * MOVED_WPB), 0, s>>>(ka);
-    return;
-  }
-  const int nb = (ka.nconf + 15) / 16;
-  if (dtype == AIQMC_F32)
-    k_moved_electron<float, N, A><<<dim3(prop_blocks(nb, MOVED_WPB)), dim3(64 * MOVED_WPB), 0, s>>>(ka);
-  else
-    k_moved_electron<double, N, A><<<dim3(prop_blocks(nb, MOVED_WPB)), dim3(64 * MOVED_WPB), 0, s>>>(ka);
+  by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    if (ka.value_only && ka.xnew) {   // pp quadrature: values only, one configuration per lane
+      const int nv = (ka.nconf + 63) / 64;
+      k_moved_value<T, N, A><<<dim3(prop_blocks(nv, MOVED_WPB)), dim3(64 * MOVED_WPB), 0, s>>>(ka);
+    } else {
+      const int nb = (ka.nconf + 15) / 16;
+      k_moved_electron<T, N, A><<<dim3(prop_blocks(nb, MOVED_WPB)), dim3(64 * MOVED_WPB), 0, s>>>(ka);
+    }
+  });
 }
 
 template <int N, int A>
 static void accept_impl(int dtype, void* pos, const AccArgs& a, int B, hipStream_t s) {
-  const int nb = (B * N + 255) / 256;
-  if (dtype == AIQMC_F32)
-    k_accept<float, N><<<dim3(nb), dim3(256), 0, s>>>((float*)pos, a, B);
-  else
-    k_accept<double, N><<<dim3(nb), dim3(256), 0, s>>>((double*)pos, a, B);
+  by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    k_accept<T, N><<<blocks(B * N, 256), dim3(256), 0, s>>>((T*)pos, a, B);
+  });
 }
 
 // per-walker parameter gradients in the kernel layout: out [nconf][Lay::total]
-template <typename T, int N, int A>
-static int pgrad_launch(const KArgs& ka, int nconf, hipStream_t s) {
-  constexpr int K = PgK<N>::value;   // walkers per wave (walker_pgrad.h)
-  constexpr int bytes = K * SmemPG<T, N, A>::bytes;
-  if (bytes > 65536) {
-    hipError_t e = hipFuncSetAttribute((const void*)&k_param_grad<T, N, A, K>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    if (e != hipSuccess) return fail(AIQMC_EHIP, std::string("hipFuncSetAttribute: ") + hipGetErrorString(e));
-  }
-  k_param_grad<T, N, A, K><<<dim3((nconf + K - 1) / K), dim3(64), bytes, s>>>(ka);
-  return 0;
-}
-
 template <int N, int A>
 static int pgrad_impl(int dtype, const KArgs& ka, int nconf, hipStream_t s) {
-  if (dtype == AIQMC_F32) {
-    if (int rc = pgrad_launch<float, N, A>(ka, nconf, s)) return rc;
-  } else {
-    if (int rc = pgrad_launch<double, N, A>(ka, nconf, s)) return rc;
+  return by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    constexpr int K = PgK<N>::value;   // walkers per wave (walker_pgrad.h)
+    constexpr int bytes = K * SmemPG<T, N, A>::bytes;
+    if (int rc = raise_lds((const void*)&k_param_grad<T, N, A, K>, bytes)) return rc;
+    k_param_grad<T, N, A, K><<<dim3((nconf + K - 1) / K), dim3(64), bytes, s>>>(ka);
+    return 0;
+  });
+}
+
+// dynamic LDS bytes and waves per workgroup of the launches that take dynamic LDS, by AIQMC_LDS_* kind
+template <typename T, int N, int A>
+static void launch_table(int* lds, int* waves) {
+  constexpr int WP = RevWpb<T, true>::value, WW = RevWpb<T, false>::value;
+  const int b[6] = {WP * SmemRev<T, N, A, kFwdReg>::bytes, WW * SmemRev<T, N, A>::bytes, SmemRev<T, N, A>::bytes,
+                    SmemLap<T, N, A>::bytes, PgK<N>::value * SmemPG<T, N, A>::bytes, Smem<T, N, true>::bytes};
+  const int w[6] = {WP, WW, 1, 0, 1, 1};   // 0: the launch chooses (k_walker_lap: 1, 2 or 4 waves)
+  for (int k = 0; k < 6; ++k) {
+    lds[k] = b[k];
+    waves[k] = w[k];
   }
-  return 0;
 }
 
 static void phase_read_impl(unsigned long long* out) {
@@ -479,22 +490,7 @@ bool AQ_CAT(AQ_N, AQ_A)(ShapeOps* ops) {
   ops->gmap = &gmap_impl<AQ_N, AQ_A>;
   ops->pgrad = &pgrad_impl<AQ_N, AQ_A>;
   ops->wy_off = Lay<AQ_N, AQ_A>::wy;
-  {
-    constexpr int N = AQ_N, A = AQ_A;
-    const int f[6] = {RevWpb<float, true>::value * SmemRev<float, N, A, kFwdReg>::bytes,
-                      RevWpb<float, false>::value * SmemRev<float, N, A>::bytes, SmemRev<float, N, A>::bytes,
-                      SmemLap<float, N, A>::bytes, PgK<N>::value * SmemPG<float, N, A>::bytes, Smem<float, N, true>::bytes};
-    const int d[6] = {RevWpb<double, true>::value * SmemRev<double, N, A, kFwdReg>::bytes,
-                      SmemRev<double, N, A>::bytes, SmemRev<double, N, A>::bytes, SmemLap<double, N, A>::bytes,
-                      PgK<N>::value * SmemPG<double, N, A>::bytes, Smem<double, N, true>::bytes};
-    const int wf[6] = {RevWpb<float, true>::value, RevWpb<float, false>::value, 1, 0, 1, 1};
-    const int wd[6] = {RevWpb<double, true>::value, 1, 1, 0, 1, 1};
-    for (int k = 0; k < 6; ++k) {
-      ops->dyn_lds[0][k] = f[k];
-      ops->dyn_lds[1][k] = d[k];
-      ops->wg_waves[0][k] = wf[k];   // 0: the launch chooses (k_walker_lap: 1, 2 or 4 waves)
-      ops->wg_waves[1][k] = wd[k];
-    }
-  }
+  launch_table<float, AQ_N, AQ_A>(ops->dyn_lds[0], ops->wg_waves[0]);
+  launch_table<double, AQ_N, AQ_A>(ops->dyn_lds[1], ops->wg_waves[1]);
   return true;
 }

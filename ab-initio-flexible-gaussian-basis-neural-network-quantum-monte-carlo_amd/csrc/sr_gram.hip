@@ -223,17 +223,15 @@ int aiqmc_sr_gram(const void* o_re, const void* o_im, int32_t dtype, int64_t B, 
   if (!out || P <= 0 || B < 0) return fail(AIQMC_EINVAL, "sr_gram: null out, P <= 0 or B < 0");
   if (B > 0 && !o_re) return fail(AIQMC_EINVAL, "sr_gram: null o_re");
   if (P > 32768) return fail(AIQMC_EINVAL, "sr_gram: P > 32768");
+  if (!is_dtype(dtype)) return fail(AIQMC_EINVAL, "dtype must be AIQMC_F32 or AIQMC_F64");
   hipStream_t s = (hipStream_t)stream;
   const int nt = (P + SR_TILE - 1) / SR_TILE;
   const dim3 gr(nt, nt);
-  if (dtype == AIQMC_F32)
-    k_sr_gram<float><<<gr, dim3(256), 0, s>>>((const float*)o_re, (const float*)o_im, B, P, (const float*)center_re,
-                                              (const float*)center_im, out, accumulate);
-  else if (dtype == AIQMC_F64)
-    k_sr_gram<double><<<gr, dim3(256), 0, s>>>((const double*)o_re, (const double*)o_im, B, P,
-                                               (const double*)center_re, (const double*)center_im, out, accumulate);
-  else
-    return fail(AIQMC_EINVAL, "dtype must be AIQMC_F32 or AIQMC_F64");
+  by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    k_sr_gram<T><<<gr, dim3(256), 0, s>>>((const T*)o_re, (const T*)o_im, B, P, (const T*)center_re,
+                                          (const T*)center_im, out, accumulate);
+  });
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(AIQMC_EHIP, std::string("sr_gram: ") + hipGetErrorString(e));
   return AIQMC_OK;

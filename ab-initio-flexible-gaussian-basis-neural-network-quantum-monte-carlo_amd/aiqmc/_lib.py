@@ -129,6 +129,7 @@ _SIGNATURES = {
     "aiqmc_debug_set_lap_waves": (_int, [_vp, _i32]),
     "aiqmc_debug_set_proposal_reuse": (_int, [_vp, _i32]),
     "aiqmc_debug_set_obs_chunk": (_int, [_vp, _i32]),
+    "aiqmc_debug_read_draws": (_int, [_vp, _i32, _vp, _i64, _vp]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
@@ -573,6 +574,25 @@ class Context:
     def set_proposal_reuse(self, on: bool):
         """Diagnostics: proposals from the walker cache (default) or recomputed from scratch."""
         check(self._lib.aiqmc_debug_set_proposal_reuse(self._h, 1 if on else 0), "aiqmc_debug_set_proposal_reuse")
+
+    def _read_draws(self, which: int, shape) -> torch.Tensor:
+        out = torch.empty(shape, dtype=self.dtype, device=self.device)
+        with torch.cuda.device(self.device):
+            check(self._lib.aiqmc_debug_read_draws(self._h, int(which), _ptr(out), out.numel(), _stream(self.device)),
+                  "aiqmc_debug_read_draws")
+        return out
+
+    def last_draws(self, B: int):
+        """Diagnostics: the draws the last Philox sweep of B walkers left in the context
+        (mc_step's last sweep, dmc_drift_diffusion): (gauss1 [B, 3N], gauss2 [B, N, 3], u [B, N]),
+        copied on the current stream."""
+        B, N = int(B), self.N
+        return self._read_draws(0, (B, 3 * N)), self._read_draws(1, (B, N, 3)), self._read_draws(2, (B, N))
+
+    def last_rotations(self, B: int) -> torch.Tensor:
+        """Diagnostics: the Haar rotations [B, 3, 3] of the last Philox local_energy_ecp or
+        dmc_tmoves call on B walkers, copied on the current stream."""
+        return self._read_draws(3, (int(B), 3, 3))
 
     def phase_cycles(self):
         """Diagnostics (AQ_PHASE_PROF builds): per-phase cycle sums [32], then cleared."""

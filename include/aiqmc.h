@@ -429,6 +429,16 @@ int aiqmc_debug_set_fuse_reduce(aiqmc_ctx* ctx, int32_t on);
 int aiqmc_debug_limdrift_factor(aiqmc_ctx* ctx, const void* sumsq, int32_t n, double tstep, int32_t mode,
                                 double* out, void* stream);
 
+/* Diagnostics: read back the draws the last AIQMC_RNG_PHILOX call left in the context, to compare
+ * them with a host replica of the generator (oracle/philox.py).  which: 0 = gauss1 [B][3N],
+ * 1 = gauss2 [B][N][3], 2 = u [B][N] (the last sweep of aiqmc_mc_step / aiqmc_dmc_drift_diffusion),
+ * 3 = the rotations [B][3][3] of aiqmc_local_energy_ecp* / aiqmc_dmc_tmoves.  A stream-ordered
+ * device-to-device copy of `count` elements of the context's dtype to the device buffer dst; no
+ * kernel is launched and no state changes.  AIQMC_EINVAL for a null context or destination, a
+ * negative count, an unknown `which`, or more elements than the buffer holds (an unallocated
+ * buffer holds none). */
+int aiqmc_debug_read_draws(aiqmc_ctx* ctx, int32_t which, void* dst, int64_t count, void* stream);
+
 /* Development builds (-DAQ_ABLATE) only: skip proposal-kernel phases (bit mask, walker_rev.h) to
  * time their marginal cost; results are meaningless.  No effect in product builds. */
 int aiqmc_debug_set_ablate(aiqmc_ctx* ctx, int32_t mask);

@@ -16,6 +16,9 @@ network_np  independent numpy restatement of the forward pass (value only)
 hamiltonian potentials + kinetic energy via jvp-of-grad (the reference's
             ``Energy/hamiltonian.py:100-131`` algorithm) and via Hessian trace
 mcstep      ``VMC/VMCmcstep.py`` walkers_update with host-injected randoms
+philox      float64 replica of the device Philox draws (``csrc/jets.h``): what a
+            sampler draws in ``AIQMC_RNG_PHILOX`` mode, as a function of
+            (seed, step, stream id, kind)
 
 Pinning status (see DESIGN.md "Oracle")
 ---------------------------------------

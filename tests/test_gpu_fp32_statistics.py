@@ -52,7 +52,7 @@ def _chain(name, dtype):
     atoms = torch.tensor(np.asarray(s.atoms), dtype=torch.float64, device="cuda")
     rows = []
     for it in range(WARM + ITERS):
-        acc = ctx.mc_step(pos, NSTEPS, TSTEP, seed=7, offset=it, count_accepts=True)
+        acc = ctx.mc_step(pos, NSTEPS, TSTEP, seed=7, offset=it * NSTEPS, count_accepts=True)
         el, _, _ = ctx.local_energy(pos)
         if it < WARM:
             continue

@@ -583,7 +583,7 @@ struct SmemQG {
 // WALK = true: the walker launch of a sweep (k_walker_rev's walker path): the previous sweep's
 // acceptance (fused), every electron's stage on lane 4c + e (its local Jacobians stay in the
 // lane's registers for B4), the full pair stream on lane k N + i, and the complete walker cache
-// (WCache, including the pair tanh's and the pivot record the one-wave proposal path reads).
+// (WCache, including the pair records (pt_rec) and the pivot record the one-wave proposal path reads).
 // 5 <= N <= 8 (round 4; the C atom all-electron (6, 1), C2 (8, 2) -- the reference's example/C2):
 // the proposals two configurations per wave, one 32-lane slot each, with the same phases: the
 // spin-group class sums take one lane exchange across the slot's two 16-lane rows, the Gauss-Jordan
@@ -727,9 +727,9 @@ __global__ __launch_bounds__(64) void k_quad_grad(KArgs ka) {
           for (int m = 0; m < 4; ++m) z += pp[m] * dw[m * 4 + o];
           q[o] = f_tanh(z);
         }
-        if (pl && !diag && act) {   // walker cache: t_{j+1} of pair (k, i) (the one-wave proposal path)
+        if (pl && !diag && act) {   // walker cache: the record (pt_rec) of t_{j+1} of pair (k, i) (the one-wave proposal path)
 #pragma unroll
-          for (int o = 0; o < 4; ++o) Wc[WC::pt + (k * N + i) * 8 + j * 4 + o] = q[o];
+          for (int o = 0; o < 4; ++o) Wc[WC::pt + (k * N + i) * 8 + j * 4 + o] = pt_rec(q[o]);
         }
 #pragma unroll
         for (int o = 0; o < 4; ++o) {

@@ -73,6 +73,25 @@ constexpr bool kFwdReg = true;
 #else
 constexpr bool kFwdReg = false;
 #endif
+// B3 of a proposal takes the moved electron's 2(N-1) pair records from F2 of the same wave (an LDS
+// block of the proposal layout) instead of running both double layers again for them
+// (-DAQ_NO_B3_HANDOVER: the recompute; DESIGN.md section 4 "Round 7").
+#ifndef AQ_NO_B3_HANDOVER
+constexpr bool kB3Handover = true;
+#else
+constexpr bool kB3Handover = false;
+#endif
+// A pair's record for B3 (the walker cache's WCache::pt and the handover block): per double layer
+// the four tanh derivative factors RSQ2 (1 - t^2), formed once where the tanh is computed, instead
+// of the tanh outputs t (-DAQ_PT_TANH), from which every reader formed them again.
+#ifndef AQ_PT_TANH
+constexpr bool kPtFactor = true;
+#else
+constexpr bool kPtFactor = false;
+#endif
+template <typename T> __device__ __forceinline__ T pt_rec(T t) {
+  return kPtFactor ? T(0.70710678118654752) * (T(1) - t * t) : t;
+}
 template <typename T, int N, int A, bool FWDREG = false, bool COMPACT = false>
 struct SmemRev {
   static constexpr int D0 = 4 * A;               // layer-0 h width
@@ -112,7 +131,12 @@ struct SmemRev {
   static_assert(zr + 4 <= g2 + 3 * 2 * N * 4, "slot table outside the g2 region");
   // FWDREG (proposals): the e-n Jastrow gradient of the direction lanes, parked from F2 to B4
   static constexpr int jdo = R + R_n;
-  static constexpr int end = jdo + (FWDREG ? 64 : 0);
+  // FWDREG (proposals): F2's records of the moved electron's pairs for B3, [2][2][16][4]: (pair
+  // (pi, o) | pair (o, pi)) x (layer 1 | layer 2) x o x 4 -- 16-byte rows at a 16-byte stride, so
+  // that both the writes (lane o) and B3's reads (o = the pair's other electron) spread over the banks
+  static constexpr bool hand = FWDREG && kB3Handover;
+  static constexpr int th = (jdo + (FWDREG ? 64 : 0) + 3) / 4 * 4;
+  static constexpr int end = hand ? th + 2 * 2 * 16 * 4 : jdo + (FWDREG ? 64 : 0);
   static constexpr int bytes = ((end * (int)sizeof(T)) + 15) & ~15;
   static constexpr int hoff(int l) { return l == 0 ? 0 : N * D0; }   // l = 0 or 3
 };
@@ -132,7 +156,7 @@ struct WCache {
   static constexpr int g2 = jaed + 48;              // [3][2][N][4]
   static constexpr int jee = g2 + 3 * 2 * N * 4;    // [1]        J_ee
   static constexpr int pv = jee + 1;                // [3N+2]     Gauss-Jordan pivot record (gj.h)
-  static constexpr int pt = ((pv + 3 * N + 2 + 3) / 4) * 4; // [N][N][8]  tanh outputs t1, t2 of pair (k, i)
+  static constexpr int pt = ((pv + 3 * N + 2 + 3) / 4) * 4; // [N][N][8]  pt_rec of the tanh outputs t1, t2 of pair (k, i)
   static constexpr int size = ((pt + 8 * N * N + 63) / 64) * 64;
 };
 // Per-proposal electron-local stage of the moved electron (k_moved_electron).
@@ -149,8 +173,9 @@ struct ECache {
   static constexpr int size = ((xp + 3 + 15) / 16) * 16;
 };
 
+// tq: the two double layers' tanh outputs as well (what B3 needs of the pair)
 template <typename T, int N, int A>
-__device__ __forceinline__ void pair_values(const T d[3], cptr<T> P, T out[3][4]) {
+__device__ __forceinline__ void pair_values(const T d[3], cptr<T> P, T out[3][4], T tq[2][4]) {
   using Ly = Lay<N, A>;
   const T RSQ2 = T(0.70710678118654752);
   T p[4];
@@ -173,10 +198,16 @@ __device__ __forceinline__ void pair_values(const T d[3], cptr<T> P, T out[3][4]
     }
 #pragma unroll
     for (int o = 0; o < 4; ++o) {
+      tq[j][o] = q[o];
       p[o] = (p[o] + q[o]) * RSQ2;
       out[j + 1][o] = p[o];
     }
   }
+}
+template <typename T, int N, int A>
+__device__ __forceinline__ void pair_values(const T d[3], cptr<T> P, T out[3][4]) {
+  T tq[2][4];
+  pair_values<T, N, A>(d, P, out, tq);
 }
 
 // Sum of x over the lanes 4i+f with equal f (i.e. over electrons, per unit f); every
@@ -504,8 +535,8 @@ template <typename T, bool PROP, bool PREP = false> struct RevWpb {
   } while (0)
 #endif
 
-// One ordered pair (k, i) of B3 (walker_rev's pair adjoints): forward values (fresh) or the cached
-// t1, t2, then the adjoints back through the two double layers to d = x_i - x_k, into dbar
+// One ordered pair (k, i) of B3 (walker_rev's pair adjoints): forward values (fresh) or the pair's
+// record tcache (pt_rec of the two layers' tanh outputs t1, t2), then the adjoints back through the two double layers to d = x_i - x_k, into dbar
 // (a function so that both waves of a split walker launch can run it on their share of the pairs).
 // may_fresh (compile-time after unrolling): the pair may recompute its forward values; fresh
 // selects them per lane without a branch (a divergent branch here turned the uniform weights
@@ -552,8 +583,8 @@ __device__ __forceinline__ void b3_pair_adjoint(cptr<T> P, const T* xs, const T*
     }
 #pragma unroll
     for (int o = 0; o < 4; ++o) {
-      t1[o] = fresh ? f1[o] : t1[o];
-      t2[o] = fresh ? f2[o] : t2[o];
+      t1[o] = fresh ? pt_rec(f1[o]) : t1[o];
+      t2[o] = fresh ? pt_rec(f2[o]) : t2[o];
     }
   }
   // adjoints: output of layer l feeds g2[l][G][i] with weight 1/|G|
@@ -562,7 +593,7 @@ __device__ __forceinline__ void b3_pair_adjoint(cptr<T> P, const T* xs, const T*
   for (int f = 0; f < 4; ++f) pb2[f] = g2b[((2 * 2 + G) * N + i) * 4 + f];
   T z2[4];
 #pragma unroll
-  for (int o = 0; o < 4; ++o) z2[o] = pb2[o] * RSQ2 * (T(1) - t2[o] * t2[o]);
+  for (int o = 0; o < 4; ++o) z2[o] = kPtFactor ? pb2[o] * t2[o] : pb2[o] * RSQ2 * (T(1) - t2[o] * t2[o]);
 #pragma unroll
   for (int m = 0; m < 4; ++m) {
     T s = g2b[((1 * 2 + G) * N + i) * 4 + m] + pb2[m] * RSQ2;
@@ -572,7 +603,7 @@ __device__ __forceinline__ void b3_pair_adjoint(cptr<T> P, const T* xs, const T*
   }
   T z1[4];
 #pragma unroll
-  for (int o = 0; o < 4; ++o) z1[o] = pb1[o] * RSQ2 * (T(1) - t1[o] * t1[o]);
+  for (int o = 0; o < 4; ++o) z1[o] = kPtFactor ? pb1[o] * t1[o] : pb1[o] * RSQ2 * (T(1) - t1[o] * t1[o]);
 #pragma unroll
   for (int m = 0; m < 4; ++m) {
     T s = g2b[((0 * 2 + G) * N + i) * 4 + m] + pb1[m] * RSQ2;
@@ -753,8 +784,19 @@ k_walker_rev(KArgs ka) {
     T d[3];
 #pragma unroll
     for (int c = 0; c < 3; ++c) d[c] = (part < 2) ? xs[os * 3 + c] - xp[c] : xp[c] - xs[os * 3 + c];
-    T v[3][4];
-    pair_values<T, N, A>(d, P, v);
+    T v[3][4], tq[2][4];
+    pair_values<T, N, A>(d, P, v, tq);
+    if constexpr (SM::hand) {
+      // the pairs at the new position, for B3: part 0 lane o is pair (pi, o), part 2 lane o is (o, pi)
+      if ((part & 1) == 0 && o < N && o != pi) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+          T* th = (T*)__builtin_assume_aligned(sm + SM::th + (((part >> 1) * 2 + j) * 16 + o) * 4, 16);
+#pragma unroll
+          for (int f = 0; f < 4; ++f) th[f] = pt_rec(tq[j][f]);
+        }
+      }
+    }
     if constexpr (compact) {
       // new - old: part 1 (3) sends its values to part 0 (2) sixteen lanes down; D[16 (part / 2) + o]
 #pragma unroll
@@ -1025,10 +1067,10 @@ k_walker_rev(KArgs ka) {
               for (int m = 0; m < 4; ++m) s += p[m] * dwv[j][m * 4 + o];
               q[o] = f_tanh(s);
             }
-            if (!PREP && !isprop && icol && !diag) {   // walker cache: t_{j+1} of pair (k, i)
+            if (!PREP && !isprop && icol && !diag) {   // walker cache: the record (pt_rec) of t_{j+1} of pair (k, i)
               T* tp = Wc + WC::pt + (k * N + ii) * 8 + j * 4;
 #pragma unroll
-              for (int o = 0; o < 4; ++o) tp[o] = q[o];
+              for (int o = 0; o < 4; ++o) tp[o] = pt_rec(q[o]);
             }
             if (PREP && icol) {   // LapCache: the same for k_walker_lap, the diagonal's finite values included
               T* tp = Lw + LCc::pt + (k * N + ii) * LCc::pt_n + j * 4;
@@ -2064,9 +2106,9 @@ k_walker_rev(KArgs ka) {
   // ------------------------------------------------------------------ B3 pair adjoints d(logpsi)/d(x_i - x_k)
   T* dbar = sm + SM::dbar;
   // Proposals from the walker cache: the 2(N-1) pairs of the moved electron pi come first
-  // (iteration 0) and recompute their forward values; every other pair takes t1, t2
-  // from walker pb's cache, so iterations >= 1 skip the forward recompute.
-  // one ordered pair (k, i): forward values (fresh) or the cached t1, t2 of walker pb, then the
+  // (iteration 0) with the records F2 handed over (or recompute their forward values); every
+  // other pair takes its record from walker pb's cache.
+  // one ordered pair (k, i): forward values (fresh) or the pair's record, then the
   // adjoints back through the two double layers to d = x_i - x_k
   auto pair_adjoint = [&](int k, int i, bool may_fresh, bool fresh, const T* tcache, T cusp, T al) {
     b3_pair_adjoint<T, N, A>(P, xs, g2b, dbar, nup, k, i, may_fresh, fresh, tcache, cusp, al);
@@ -2074,10 +2116,10 @@ k_walker_rev(KArgs ka) {
   constexpr int NPR = N * (N - 1);
   if (reuse && !AQ_ABL(32)) {
     // Proposals: iteration u of lane l is pair index it = l + 64 u.  The 2(N-1) pairs of the
-    // moved electron pi (it < M, all in iteration 0) recompute their forward values; every
-    // other pair takes t1, t2 from walker pb's cache.  All cached loads of the lane are issued
-    // before the first pair is processed, so their latency overlaps the fresh pairs' tanh's
-    // and the earlier iterations (instead of one exposed cache round trip per iteration).
+    // moved electron pi are it < M, all in iteration 0; every other pair takes its record from
+    // walker pb's cache.  All cached loads of the lane are issued before the first pair is
+    // processed, so their latency overlaps the earlier iterations (instead of one exposed cache
+    // round trip per iteration).
     constexpr int M = 2 * (N - 1);
     constexpr int NIT = (NPR + 63) / 64;
     T tc[NIT][8], jc[NIT], ja[NIT];
@@ -2095,15 +2137,30 @@ k_walker_rev(KArgs ka) {
 #pragma unroll
     for (int u = 0; u < NIT; ++u) {
       const int k = pk[u], i = pi2[u];
-      // loaded on every lane (the fresh pairs of iteration 0 select their own values)
+      // loaded on every lane (pi's pairs of iteration 0 select their own values)
       const T* tp = Wc + WC::pt + (k * N + i) * 8;
 #pragma unroll
       for (int o = 0; o < 8; ++o) tc[u][o] = tp[o];
     }
+    if constexpr (SM::hand) {
+      // iteration 0: the records of pi's pairs at the proposed position come from F2's handover
+      // block (row o = the pair's other electron; the other lanes read a row they do not use)
+      const int hp = pk[0] == pi ? 0 : 1, ho = pk[0] == pi ? pi2[0] : pk[0];
+      T hv[8];   // read by every lane, selected afterwards (a read under the select becomes a branch)
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const T* th = (const T*)__builtin_assume_aligned(sm + SM::th + ((hp * 2 + j) * 16 + ho) * 4, 16);
+#pragma unroll
+        for (int f = 0; f < 4; ++f) hv[j * 4 + f] = th[f];
+      }
+#pragma unroll
+      for (int o = 0; o < 8; ++o) tc[0][o] = lane < M ? hv[o] : tc[0][o];
+    }
 #pragma unroll
     for (int u = 0; u < NIT; ++u) {
       const int it = lane + 64 * u;
-      if (it < NPR) pair_adjoint(pk[u], pi2[u], u == 0, u == 0 && it < M, tc[u], jc[u], ja[u]);
+      const bool rc = !SM::hand && u == 0;   // without the handover iteration 0 recomputes pi's pairs
+      if (it < NPR) pair_adjoint(pk[u], pi2[u], rc, rc && it < M, tc[u], jc[u], ja[u]);
       if (lv_at == u + 1) lv_load();
     }
   } else if (!reuse) {

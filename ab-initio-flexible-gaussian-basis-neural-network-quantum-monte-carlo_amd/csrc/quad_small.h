@@ -84,12 +84,7 @@ struct SmemQ {
 // pivot search per step.  A slot whose pivot k falls below 0.1 of its walker's (or out of the float
 // range) reruns the pivoted LU.  A quadrature configuration moves one electron far (onto the sphere
 // around an atom), and still 2.9 % of C2 ccECP configurations need the rerun (CPU experiment on the
-// fp64 oracle's matrices).  -DAQ_QUAD_PIVOTED: the pivoted LU always.
-#ifndef AQ_QUAD_PIVOTED
-constexpr bool kQuadFixedLU = true;
-#else
-constexpr bool kQuadFixedLU = false;
-#endif
+// fp64 oracle's matrices).  KArgs::quad_pivoted: the pivoted LU for every slot.
 
 // F1 of the packed kernels: walker pb's cached stage (positions X, walker cache Wc) with electron
 // pi's entries from its moved-electron record Eq, into the slot's LDS block.  Every load is
@@ -185,7 +180,7 @@ __global__ __launch_bounds__(64) void k_quad_value(KArgs ka) {
   // ---------------------------------------------------------------- F1 cached stage of walker pb
   T jsum = quad_stage_load<T, N, A, SW>((const T*)ka.pos + (size_t)pb * 3 * N, Wc, Eq, pi, sl, xs, sm + SQ::xo,
                                         Yv, hl, g2);
-  if constexpr (kQuadFixedLU) {   // the walker's pivot record (order, 1 / |pivot|, parity) for F5
+  {   // the walker's pivot record (order, 1 / |pivot|, parity) for F5
     const T v = Wc[WC::pv + (sl < 2 * N + 1 ? sl : 2 * N)];
     if (sl < 2 * N + 1) sm[SQ::pv + sl] = v;
   }
@@ -395,36 +390,32 @@ __global__ __launch_bounds__(64) void k_quad_value(KArgs ka) {
         }
       }
     };
-    if constexpr (kQuadFixedLU) {
-      // the walker's order: pivot row p of step k and 1 / |walker pivot k| from the slot's LDS copy
-      T a = a0, b = b0;
-      bool bad = ka.quad_pivoted != 0, done = false;
+    // the walker's order: pivot row p of step k and 1 / |walker pivot k| from the slot's LDS copy
+    T a = a0, b = b0;
+    bool bad = ka.quad_pivoted != 0, done = false;
 #pragma unroll
-      for (int k = 0; k < N; ++k) {
-        const T akr = k == 0 ? quad_bcast<0>(a) : (k == 1 ? quad_bcast<1>(a) : (k == 2 ? quad_bcast<2>(a) : quad_bcast<3>(a)));
-        const T aki = k == 0 ? quad_bcast<0>(b) : (k == 1 ? quad_bcast<1>(b) : (k == 2 ? quad_bcast<2>(b) : quad_bcast<3>(b)));
-        const int p = (int)sm[SQ::pv + k];
-        const T rk = sm[SQ::pv + N + k];
-        const T er = __shfl(a, rowbase + 4 * p + c), ei = __shfl(b, rowbase + 4 * p + c);   // A[p][c]
-        // A[p][k]: lane c = k of this quad holds it in er
-        const T pr = k == 0 ? quad_bcast<0>(er) : (k == 1 ? quad_bcast<1>(er) : (k == 2 ? quad_bcast<2>(er) : quad_bcast<3>(er)));
-        const T pim = k == 0 ? quad_bcast<0>(ei) : (k == 1 ? quad_bcast<1>(ei) : (k == 2 ? quad_bcast<2>(ei) : quad_bcast<3>(ei)));
-        done = done || (p == r);
-        T ipr, ipi, rabs;
-        pivot_step(pr, pim, ipr, ipi, rabs);
-        bad = bad || !(rk >= T(0.1) * rabs);   // |pivot| below 0.1 of the walker's (or not finite)
-        if (rl && !done) {
-          const T mr = akr * ipr - aki * ipi, mi = akr * ipi + aki * ipr;
-          a -= mr * er - mi * ei;
-          b -= mr * ei + mi * er;
-        }
+    for (int k = 0; k < N; ++k) {
+      const T akr = k == 0 ? quad_bcast<0>(a) : (k == 1 ? quad_bcast<1>(a) : (k == 2 ? quad_bcast<2>(a) : quad_bcast<3>(a)));
+      const T aki = k == 0 ? quad_bcast<0>(b) : (k == 1 ? quad_bcast<1>(b) : (k == 2 ? quad_bcast<2>(b) : quad_bcast<3>(b)));
+      const int p = (int)sm[SQ::pv + k];
+      const T rk = sm[SQ::pv + N + k];
+      const T er = __shfl(a, rowbase + 4 * p + c), ei = __shfl(b, rowbase + 4 * p + c);   // A[p][c]
+      // A[p][k]: lane c = k of this quad holds it in er
+      const T pr = k == 0 ? quad_bcast<0>(er) : (k == 1 ? quad_bcast<1>(er) : (k == 2 ? quad_bcast<2>(er) : quad_bcast<3>(er)));
+      const T pim = k == 0 ? quad_bcast<0>(ei) : (k == 1 ? quad_bcast<1>(ei) : (k == 2 ? quad_bcast<2>(ei) : quad_bcast<3>(ei)));
+      done = done || (p == r);
+      T ipr, ipi, rabs;
+      pivot_step(pr, pim, ipr, ipi, rabs);
+      bad = bad || !(rk >= T(0.1) * rabs);   // |pivot| below 0.1 of the walker's (or not finite)
+      if (rl && !done) {
+        const T mr = akr * ipr - aki * ipi, mi = akr * ipi + aki * ipr;
+        a -= mr * er - mi * ei;
+        b -= mr * ei + mi * er;
       }
-      inv = (int)sm[SQ::pv + 2 * N];
-      const unsigned long long bm = __ballot(bad);
-      if ((bm >> (lane & ~(SW - 1))) & ((1ull << SW) - 1ull)) pivoted();   // this slot: partial pivoting
-    } else {
-      pivoted();
     }
+    inv = (int)sm[SQ::pv + 2 * N];
+    const unsigned long long bm = __ballot(bad);
+    if ((bm >> (lane & ~(SW - 1))) & ((1ull << SW) - 1ull)) pivoted();   // this slot: partial pivoting
   } else {
     // 5 <= N <= 8: lane 4r + g of the slot holds A[r][g] and A[r][g + 4] (row r, two columns).
     // Column k reaches the lanes of its row by one quad broadcast; the pivot of column k is the
@@ -515,26 +506,22 @@ __global__ __launch_bounds__(64) void k_quad_value(KArgs ka) {
         lu_step(k, p, a, b, rl && !((used >> r) & 1u), akr, aki, rabs);
       }
     };
-    if constexpr (kQuadFixedLU) {
-      T a[2] = {a0[0], a0[1]}, b[2] = {b0[0], b0[1]};
-      bool bad = ka.quad_pivoted != 0, done = false;
+    T a[2] = {a0[0], a0[1]}, b[2] = {b0[0], b0[1]};
+    bool bad = ka.quad_pivoted != 0, done = false;
 #pragma unroll
-      for (int k = 0; k < N; ++k) {
-        T akr, aki;
-        col_k(k, a, b, akr, aki);
-        const int p = (int)sm[SQ::pv + k];
-        const T rk = sm[SQ::pv + N + k];
-        done = done || (p == r);
-        T rabs;
-        lu_step(k, p, a, b, rl && !done, akr, aki, rabs);
-        bad = bad || !(rk >= T(0.1) * rabs);   // |pivot| below 0.1 of the walker's (or not finite)
-      }
-      inv = (int)sm[SQ::pv + 2 * N];
-      const unsigned long long bm = __ballot(bad);
-      if ((bm >> (lane & ~(SW - 1))) & ((1ull << SW) - 1ull)) pivoted();   // this slot: partial pivoting
-    } else {
-      pivoted();
+    for (int k = 0; k < N; ++k) {
+      T akr, aki;
+      col_k(k, a, b, akr, aki);
+      const int p = (int)sm[SQ::pv + k];
+      const T rk = sm[SQ::pv + N + k];
+      done = done || (p == r);
+      T rabs;
+      lu_step(k, p, a, b, rl && !done, akr, aki, rabs);
+      bad = bad || !(rk >= T(0.1) * rabs);   // |pivot| below 0.1 of the walker's (or not finite)
     }
+    inv = (int)sm[SQ::pv + 2 * N];
+    const unsigned long long bm = __ballot(bad);
+    if ((bm >> (lane & ~(SW - 1))) & ((1ull << SW) - 1ull)) pivoted();   // this slot: partial pivoting
   }
   const T jt = slot_sum<SW>(jsum);
   if (act && sl == 0) {

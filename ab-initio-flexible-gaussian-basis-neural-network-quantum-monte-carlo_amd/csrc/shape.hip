@@ -247,7 +247,7 @@ static int set_lds_t() {
   if (int rc = raise_lds((const void*)&k_walker_rev<T, N, A>, SmemRev<T, N, A>::bytes)) return rc;
   // proposal launches: RevWpb configurations per workgroup.  fp32 only: an fp64 proposal workgroup
   // holds one configuration, within the default limit for every shape
-  constexpr int pb = RevWpb<T, true>::value * SmemRev<T, N, A, kFwdReg>::bytes;
+  constexpr int pb = RevWpb<T, true>::value * SmemRev<T, N, A, true>::bytes;
   if constexpr (sizeof(T) == 4) return raise_lds((const void*)&k_walker_rev<T, N, A, false, true>, pb);
   else static_assert(pb <= 65536, "fp64 proposal launches need the raised LDS limit too");
   return 0;
@@ -311,29 +311,6 @@ static bool quad_small(const KArgs& ka, int nconf, hipStream_t s) {
   return false;
 }
 
-// fp32 N2 proposals of small batches (the per-rank share of a strong-scaling run): the PW7
-// instantiation (7 waves/SIMD, compact LDS; walker_rev.h) when it needs fewer rounds of waves than
-// the 5-wave one and the batch takes at most three of those.  Measured slower at every batch size
-// (N2, 512 / 1024 / 2048 walkers: proposal launch 40.3 -> 43.8, 65.9 -> 74.5, 116.0 -> 130.2 us,
-// profiles/r04_s8_ab_pw7.txt), so it is compiled only with -DAQ_PW7 (AIQMC_PW7=0 / 1 forces it
-// off / on there).
-#ifdef AQ_PW7
-static bool use_pw7(int nconf) {
-  static const int force = [] {
-    const char* e = std::getenv("AIQMC_PW7");
-    return e ? (e[0] == '0' ? 0 : 1) : -1;
-  }();
-  if (force >= 0) return force == 1;
-  int dev = 0, ncu = 256;
-  if (hipGetDevice(&dev) != hipSuccess ||
-      hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0)
-    ncu = 256;
-  const long s5 = 20L * ncu, s7 = 28L * ncu;
-  const long r5 = (nconf + s5 - 1) / s5, r7 = (nconf + s7 - 1) / s7;
-  return r7 < r5 && r5 <= 3;
-}
-#endif
-
 // Which kernel a walker launch reaches (ops.walker): the first row that matches, from the top.
 // The launch kind is not named, it is read off the KArgs fields.  T = the dtype; n = nconf;
 // Wp = RevWpb<T, true>, Ww = RevWpb<T, false> configurations per workgroup (both 1 for fp64);
@@ -346,16 +323,14 @@ static bool use_pw7(int nconf) {
 //  3  GRAD      N <= 8, !proposal, wcache, !value_only, !orb,       k_quad_grad<T, walker>      ceil(n / NSL)       64     0
 //               !lapcache, !one_wave
 //  4  LAP       --                                                  k_walker<T, MODE_LAP>       n                   64     Smem<T, N, true>
-//  5  GRAD      proposal, ecache, fp32, (N, A) = (14, 2), a         k_walker_rev<PROP, PW7>     prop_blocks(n, Wp)  64 Wp  Wp SmemRev<kFwdReg, PW7>
-//               -DAQ_PW7 build, use_pw7(n)
-//  6  GRAD      proposal, ecache                                    k_walker_rev<T, PROP>       prop_blocks(n, Wp)  64 Wp  Wp SmemRev<T, kFwdReg>
-//  7  GRAD      fp32, walk_split, !proposal, !value_only,           k_walker_rev<float, SPL>    n                   128    SmemRev<float>
+//  5  GRAD      proposal, ecache                                    k_walker_rev<T, PROP>       prop_blocks(n, Wp)  64 Wp  Wp SmemRev<T, true>
+//  6  GRAD      fp32, walk_split, !proposal, !value_only,           k_walker_rev<float, SPL>    n                   128    SmemRev<float>
 //               not AIQMC_WALK_SPLIT=0
-//  8  GRAD      --                                                  k_walker_rev<T>             ceil(n / Ww)        64 Ww  Ww SmemRev<T>
-//  9  GRAD_FWD  --                                                  k_walker<T, MODE_GRAD>      n                   64     Smem<T, N, false>
+//  7  GRAD      --                                                  k_walker_rev<T>             ceil(n / Ww)        64 Ww  Ww SmemRev<T>
+//  8  GRAD_FWD  --                                                  k_walker<T, MODE_GRAD>      n                   64     Smem<T, N, false>
 //
 // So proposals without an ecache (proposal reuse off) and value_only / orb walker launches take row
-// 8.  Rows 5 and 7 are instantiated for float alone; every other row for both dtypes.
+// 7.  Row 6 is instantiated for float alone; every other row for both dtypes.
 template <typename T, int N, int A>
 static void walker_launch(int mode, const KArgs& ka, int nconf, hipStream_t s) {
   if (mode == MODE_GRAD && quad_small<T, N, A>(ka, nconf, s)) return;
@@ -363,21 +338,12 @@ static void walker_launch(int mode, const KArgs& ka, int nconf, hipStream_t s) {
     k_walker<T, N, A, MODE_LAP><<<dim3(nconf), dim3(64), Smem<T, N, true>::bytes, s>>>(ka);
   } else if (mode == MODE_GRAD && ka.proposal && ka.ecache) {   // proposals from the walker cache
     constexpr int W = RevWpb<T, true>::value;
-#ifdef AQ_PW7
-    if constexpr (sizeof(T) == 4 && N == 14 && A == 2) {
-      if (use_pw7(nconf)) {
-        k_walker_rev<T, N, A, false, true, true><<<dim3(prop_blocks(nconf, W)), dim3(64 * W),
-                                                  W * SmemRev<T, N, A, kFwdReg, true>::bytes, s>>>(ka);
-        return;
-      }
-    }
-#endif
     k_walker_rev<T, N, A, false, true><<<dim3(prop_blocks(nconf, W)), dim3(64 * W),
-                                        W * SmemRev<T, N, A, kFwdReg>::bytes, s>>>(ka);
+                                        W * SmemRev<T, N, A, true>::bytes, s>>>(ka);
   } else if (mode == MODE_GRAD) {
     if constexpr (sizeof(T) == 4) {   // two waves per walker: an fp32 instantiation only
       if (ka.walk_split && !ka.proposal && !ka.value_only && walk_split_on()) {
-        k_walker_rev<T, N, A, false, false, false, false, true><<<dim3(nconf), dim3(128), SmemRev<T, N, A>::bytes, s>>>(ka);
+        k_walker_rev<T, N, A, false, false, false, true><<<dim3(nconf), dim3(128), SmemRev<T, N, A>::bytes, s>>>(ka);
         return;
       }
     }
@@ -398,7 +364,7 @@ static void walker_impl(int dtype, int mode, const KArgs& ka, int nconf, hipStre
 template <typename T, int N, int A, bool PH>
 static void lap_launch(const KArgs& k1, const KArgs& k2, int nconf, int waves, hipStream_t s) {
   const dim3 wg(64 * waves);   // waves per walker in the first-derivative pass: 1, 2 or 4
-  k_walker_rev<T, N, A, true, false, false, PH><<<dim3(nconf), dim3(64), SmemRev<T, N, A>::bytes, s>>>(k1);
+  k_walker_rev<T, N, A, true, false, PH><<<dim3(nconf), dim3(64), SmemRev<T, N, A>::bytes, s>>>(k1);
   if (waves == 1)
     k_walker_lap<T, N, A, 1, PH><<<dim3(nconf), wg, SmemLap<T, N, A>::bytes, s>>>(k2);
   else
@@ -452,7 +418,7 @@ static int pgrad_impl(int dtype, const KArgs& ka, int nconf, hipStream_t s) {
 template <typename T, int N, int A>
 static void launch_table(int* lds, int* waves) {
   constexpr int WP = RevWpb<T, true>::value, WW = RevWpb<T, false>::value;
-  const int b[6] = {WP * SmemRev<T, N, A, kFwdReg>::bytes, WW * SmemRev<T, N, A>::bytes, SmemRev<T, N, A>::bytes,
+  const int b[6] = {WP * SmemRev<T, N, A, true>::bytes, WW * SmemRev<T, N, A>::bytes, SmemRev<T, N, A>::bytes,
                     SmemLap<T, N, A>::bytes, PgK<N>::value * SmemPG<T, N, A>::bytes, Smem<T, N, true>::bytes};
   const int w[6] = {WP, WW, 1, 0, 1, 1};   // 0: the launch chooses (k_walker_lap: 1, 2 or 4 waves)
   for (int k = 0; k < 6; ++k) {

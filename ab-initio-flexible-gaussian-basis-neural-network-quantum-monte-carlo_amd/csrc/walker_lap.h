@@ -112,14 +112,9 @@ struct StageRegs {
 };
 // local-energy stage prefetch (round 6, interleaved A/B on one box, N2 4096 walkers, µs per E_L
 // pair: 194.7 / 195.1 -> 192.2 / 191.3, E_L and positions bitwise equal;
-// profiles/r06_s2_ab_lap_prefetch.txt).  -DAQ_LAP_NO_PREFETCH: the synchronous stage_copy.  Layer
+// profiles/r06_s2_ab_lap_prefetch.txt) against a synchronous stage_copy at each boundary.  Layer
 // 0's block kept in registers over the per-electron stage and E2's Phi row loaded with Q_f as well:
 // 190.1 / 189.4 vs 189.9 / 190.0, not bitwise (operand order); not kept (profiles/r06_s3_ab_lap_prefetch2.txt).
-#ifndef AQ_LAP_NO_PREFETCH
-constexpr bool kLapPrefetch = true;
-#else
-constexpr bool kLapPrefetch = false;
-#endif
 
 // One h-stream layer (nn.py:280-311) in first derivatives, column loop over electrons i.
 // ly: this layer's LapCache block (LDS); hb: dh/dx of every electron [N][49][NH], updated in place
@@ -323,85 +318,6 @@ __device__ __forceinline__ void lap_layer(cptr<T> P, const T* xs, T* hb, const T
   }
 }
 
-// E4's determinant term ss = Re sum_{r,s} S_rs S_sr, S_rs = sum_f U_rf Q_f[r,s], on the matrix
-// cores.  ss = u^T K u with u = U[(r,f)] (this direction's column of dh/dx of electron
-// rowsrc[r], hb) and
-//   K[(r,f),(s,g)] = Re(Q_f[r,s] Q_g[s,r])          (4N x 4N, symmetric, the same for every direction),
-// so V = K U for all 3N directions at once is one (4N x 4N) x (4N x 48) product:
-// v_mfma_{f32,f64}_16x16x4 with K-step s = electron s (k = unit g = lane >> 4), M-tiles over
-// rows (r, f), N-tile c = coordinate (column e = lane & 15 of tile c is direction lane 16c + e,
-// the hb column).  The A fragment (one K entry per lane) is formed from two LDS reads of Q_f;
-// the B fragment is read from hb as it stands.  Then ss = sum_i U[i] V[i] per direction: a
-// lane-local sum over the accumulator rows and a sum over the four lane groups.  Multi-wave
-// mode: wave wv takes the K-steps s = wv, wv + W, ... (ss is linear in V).  Replaces ~1,650
-// VALU FMAs and ~1,100 broadcast LDS reads per wave (the double loop over r < s) by 12 N MFMAs.
-// Opt-in (-DAQ_LAP_MFMA_SS): measured SLOWER on N2 / 4096 walkers (local-energy pair 240.8 /
-// 241.2 us against 234.0 / 234.6 us with the VALU loop, two interleaved runs, same box;
-// profiles/r03_s1_lap_mfma_ab.txt).  The quadratic form does 4x the FLOPs of the S_rs S_sr
-// loop (K is 4N x 4N dense, S is rank-structured), and f32 MFMA runs at the f32 VALU rate on
-// gfx950, so the matrix cores only pay where they overlap VALU work of the other wave.
-template <typename T> struct MfmaTile;
-template <> struct MfmaTile<float> {
-  typedef float v4 __attribute__((ext_vector_type(4)));
-  static __device__ __forceinline__ v4 mma(float a, float b, v4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-  }
-  // accumulator register v of lane group q holds row 4q + v (column = lane & 15)
-  static constexpr __device__ int row(int q, int v) { return 4 * q + v; }
-};
-template <> struct MfmaTile<double> {
-  typedef double v4 __attribute__((ext_vector_type(4)));
-  static __device__ __forceinline__ v4 mma(double a, double b, v4 c) {
-    return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
-  }
-  static constexpr __device__ int row(int q, int v) { return q + 4 * v; }   // f64 C/D map
-};
-
-template <typename T, int N>
-__device__ __forceinline__ T ss_mfma(const T* Qs, const T* hb, const int* rowsrc, int lane, int wv, int W) {
-  static_assert(NH == 4, "K-step = one electron's 4 units");
-  using MT = MfmaTile<T>;
-  using V4 = typename MT::v4;
-  constexpr int NM = (4 * N + 15) / 16;   // M-tiles over the rows (r, f)
-  const int q = lane >> 4, e = lane & 15;
-  T out = T(0);
-  // one N-tile (coordinate c) at a time: 4 NM accumulator registers live instead of 12 NM
-#pragma unroll 1
-  for (int c = 0; c < 3; ++c) {
-    V4 acc[NM];
-#pragma unroll
-    for (int m = 0; m < NM; ++m) acc[m] = V4{T(0), T(0), T(0), T(0)};
-#pragma unroll 2
-    for (int s = wv; s < N; s += W) {
-      const T bop = hb[(rowsrc[s] * 49 + 16 * c + e) * NH + q];
-#pragma unroll
-      for (int m = 0; m < NM; ++m) {
-        const int i = 16 * m + e;            // A row (r, f); A column k = unit q of electron s
-        const int r = i >> 2, f = i & 3;
-        const int rc = r < N ? r : N - 1;
-        const T* a = Qs + ((rc * N + s) * NH + f) * 2;
-        const T* b = Qs + ((s * N + rc) * NH + q) * 2;
-        T kv = a[0] * b[0] - a[1] * b[1];
-        if (4 * N % 16 != 0 && m == NM - 1) kv = r < N ? kv : T(0);
-        acc[m] = MT::mma(kv, bop, acc[m]);
-      }
-    }
-    T p = T(0);
-#pragma unroll
-    for (int m = 0; m < NM; ++m)
-#pragma unroll
-      for (int v = 0; v < 4; ++v) {
-        const int i = 16 * m + MT::row(q, v);
-        const int r = i >> 2, f = i & 3;
-        if (16 * (m + 1) <= 4 * N || r < N) p += hb[(rowsrc[r < N ? r : N - 1] * 49 + 16 * c + e) * NH + f] * acc[m][v];
-      }
-    p += __shfl_xor(p, 16);
-    p += __shfl_xor(p, 32);
-    out = (q == c) ? p : out;
-  }
-  return out;
-}
-
 // One workgroup of W = blockDim.x / 64 waves per walker (W = 1, 2 or 4; aiqmc.hip picks W so
 // that small batches still fill the chip): every wave evaluates the per-electron stage of all
 // electrons (its lanes are the 3N directions), the h-stream columns i = wv, wv + W, ... of each
@@ -484,34 +400,30 @@ __global__ __launch_bounds__(64 * WMAX) __attribute__((amdgpu_waves_per_eu(AQ_LA
   T jd2 = (!PH && w0 && dir) ? eo.jae.d2 : T(0);
 
   // ------------------------------------------------------------------ h stream, first derivatives
-  // kLapPrefetch: each staged block's loads are issued one phase ahead (into spare VGPRs: the kernel
+  // stage prefetch: each staged block's loads are issued one phase ahead (into spare VGPRs: the kernel
   // runs at 2 waves/SIMD, 256 VGPRs each) and written to LDS after the barrier that frees it, so
   // no wave waits a whole L2/HBM round trip at a stage boundary
   LPH(1);
   StageRegs<T, LC::layer_n> lnext;
-  if constexpr (kLapPrefetch) lnext.load(Lc + LC::layer_n);
+  lnext.load(Lc + LC::layer_n);
   lap_layer<T, N, A, 0>(P, xs, hb, ly, eo.hf, l49, lc, er, le, val, dir, live, nup, jd1, jd2, vv, acc, wv, W, Lpt);
   LPH(2);
   if constexpr (PH) {   // the e-e Jastrow terms and V_ee of layer 0's column loop: not part of theta
     jd1 = jd2 = vv = T(0);
   }
   __syncthreads();
-  if constexpr (kLapPrefetch) lnext.store(ly);
-  else stage_copy<T>(ly, Lc + LC::layer_n, LC::layer_n);
+  lnext.store(ly);
   __syncthreads();
-  if constexpr (kLapPrefetch) lnext.load(Lc + 2 * LC::layer_n);
+  lnext.load(Lc + 2 * LC::layer_n);
   lap_layer<T, N, A, 1>(P, xs, hb, ly, eo.hf, l49, lc, er, le, val, dir, live, nup, jd1, jd2, vv, acc, wv, W, Lpt);
   __syncthreads();
-  if constexpr (kLapPrefetch) lnext.store(ly);
-  else stage_copy<T>(ly, Lc + 2 * LC::layer_n, LC::layer_n);
+  lnext.store(ly);
   __syncthreads();
   LPH(3);
   StageRegs<T, 8 * N * N> qnext;
   StageRegs<T, (SM::stage_b ? 2 * N * N : 4)> bnext;
-  if constexpr (kLapPrefetch) {
-    qnext.load(Lc + LC::qs);
-    if constexpr (SM::stage_b) bnext.load(Lc + LC::bm);
-  }
+  qnext.load(Lc + LC::qs);
+  if constexpr (SM::stage_b) bnext.load(Lc + LC::bm);
   // E2's Phi row of electron le, issued a layer ahead (per-lane 16-byte loads of 2N contiguous values)
   T phrow[2 * N];
   if constexpr (2 * N % 4 == 0) ld_vec<T, 2 * N>(Lc + LC::ph + le * N * 2, phrow);
@@ -525,10 +437,8 @@ __global__ __launch_bounds__(64 * WMAX) __attribute__((amdgpu_waves_per_eu(AQ_LA
   LPH(4);
   // ------------------------------------------------------------------ determinant terms
   // (phases fenced so that the scheduler does not stretch their live ranges across each other)
-  const int* rowsrc = ka.rowsrc;
   const T* Qs = nullptr;                     // LDS copy, set after E1
   const T* Bu = (const T*)(Lc + LC::bm);     // LDS copy after E1 where it fits
-  const cptr<T> Ph = Lc + LC::ph;
   // row r's electron rowsrc[r] by a lane read of rsl (lane r holds it, loaded at kernel start): read
   // through the pointer, every (r, s) step of E3/E4 was a dependent global load (the kernel also writes
   // global memory, so it cannot be a scalar load) waited for before its LDS address was known
@@ -547,16 +457,8 @@ __global__ __launch_bounds__(64 * WMAX) __attribute__((amdgpu_waves_per_eu(AQ_LA
   {
     T* qd = sm + SM::qs;
     static_assert(LC::qs % 4 == 0 && LC::bm % 4 == 0 && SM::qs % 4 == 0 && SM::bs % 4 == 0, "16-byte staging");
-    if constexpr (kLapPrefetch) {
-      qnext.store(qd);
-      if constexpr (SM::stage_b) bnext.store(sm + SM::bs);
-    } else {
-      stage_copy<T>(qd, Lc + LC::qs, 8 * N * N);
-      if constexpr (SM::stage_b) {
-        T* bd = sm + SM::bs;
-        stage_copy<T>(bd, Lc + LC::bm, 2 * N * N);
-      }
-    }
+    qnext.store(qd);
+    if constexpr (SM::stage_b) bnext.store(sm + SM::bs);
   }
   __syncthreads();
   Qs = sm + SM::qs;
@@ -641,12 +543,9 @@ __global__ __launch_bounds__(64 * WMAX) __attribute__((amdgpu_waves_per_eu(AQ_LA
       si += ur[f] * Qs[((r * N + le) * NH + f) * 2 + 1];
     }
     cross += PH ? zr * si + zi * sr : zr * sr - zi * si;
-#ifndef AQ_LAP_MFMA_SS
-    constexpr bool vss = true;
-#else
-    constexpr bool vss = PH;   // the MFMA form of ss is built for the real part only
-#endif
-    if constexpr (vss) {
+    // ss on the VALU: as a quadratic form on the matrix cores (4x the FLOPs, f32 MFMA at the f32
+    // VALU rate) the local-energy pair measured 240.8 / 241.2 us against 234.0 / 234.6
+    // (profiles/r03_s1_lap_mfma_ab.txt)
     T dr = T(0), di = T(0);
 #pragma unroll
     for (int f = 0; f < NH; ++f) {
@@ -670,14 +569,7 @@ __global__ __launch_bounds__(64 * WMAX) __attribute__((amdgpu_waves_per_eu(AQ_LA
       }
       ss += T(2) * (PH ? ar * bi + ai * br : ar * br - ai * bi);
     }
-    }
   }
-#ifdef AQ_LAP_MFMA_SS
-  if constexpr (!PH) {
-    __builtin_amdgcn_sched_barrier(0);
-    ss = ss_mfma<T, N>(Qs, hb, rowsrc, lane, wv, W);
-  }
-#endif
 #undef UH
   LPH(8);
   // (w.b_e)^2: its real part, or (PH) its imaginary part 2 Re Im

@@ -63,11 +63,7 @@ template <typename T> __device__ __forceinline__ void lds_add(T* p, T v) { atomi
 // PGK x items (walker k = item / n), each walker with its own LDS block.  The Gauss-Jordan (gj.h,
 // one matrix per wave) runs once per walker.  Per walker the arithmetic and its order are those of
 // the one-walker kernel (PGK = 1).
-#ifndef AQ_PGK1
 template <int N> struct PgK { static constexpr int value = N <= 4 ? 4 : (N <= 8 ? 2 : 1); };
-#else   // A/B builds: one walker per wave
-template <int N> struct PgK { static constexpr int value = 1; };
-#endif
 
 template <typename T, int N, int A, int K = 1>
 __global__ __launch_bounds__(64) void k_param_grad(KArgs ka) {

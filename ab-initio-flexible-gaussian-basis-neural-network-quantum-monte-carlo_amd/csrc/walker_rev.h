@@ -62,37 +62,22 @@ static __device__ unsigned long long aq_phase_cycles[32];
 #define AQ_ABL(b) false
 #endif
 
-// FWDREG (proposal instantiations with AQ_FWD_REG): the conv and single-layer outputs of F4 stay
+// FWDREG (the proposal instantiations): the conv and single-layer outputs of F4 stay
 // in registers until B2 instead of the cq / sv blocks (1.68 KB less LDS per wave for N2).
 // Round 4, interleaved A/B on one box (N2, 4096 walkers, µs per proposal launch): 219.2-221.7
 // with the LDS blocks, 217.9-218.8 with registers (96 VGPRs, no spill; the same 5 waves/SIMD).
 // The LDS saving would allow 6 waves/SIMD, but at the 80-VGPR budget that needs, the kernel spills
 // 19 VGPRs and measured 230.0-231.1 (profiles/r04_s3_ab_fwdreg.txt).
-#ifndef AQ_NO_FWD_REG
-constexpr bool kFwdReg = true;
-#else
-constexpr bool kFwdReg = false;
-#endif
 // B3 of a proposal takes the moved electron's 2(N-1) pair records from F2 of the same wave (an LDS
 // block of the proposal layout) instead of running both double layers again for them
-// (-DAQ_NO_B3_HANDOVER: the recompute; DESIGN.md section 4 "Round 7").
-#ifndef AQ_NO_B3_HANDOVER
-constexpr bool kB3Handover = true;
-#else
-constexpr bool kB3Handover = false;
-#endif
+// (DESIGN.md section 4 "Round 7").
 // A pair's record for B3 (the walker cache's WCache::pt and the handover block): per double layer
 // the four tanh derivative factors RSQ2 (1 - t^2), formed once where the tanh is computed, instead
-// of the tanh outputs t (-DAQ_PT_TANH), from which every reader formed them again.
-#ifndef AQ_PT_TANH
-constexpr bool kPtFactor = true;
-#else
-constexpr bool kPtFactor = false;
-#endif
+// of the tanh outputs t, from which every reader formed them again.
 template <typename T> __device__ __forceinline__ T pt_rec(T t) {
-  return kPtFactor ? T(0.70710678118654752) * (T(1) - t * t) : t;
+  return T(0.70710678118654752) * (T(1) - t * t);
 }
-template <typename T, int N, int A, bool FWDREG = false, bool COMPACT = false>
+template <typename T, int N, int A, bool FWDREG = false>
 struct SmemRev {
   static constexpr int D0 = 4 * A;               // layer-0 h width
   static constexpr int DFM = 3 * D0 + 8;         // widest conv input (layer 0)
@@ -112,14 +97,10 @@ struct SmemRev {
   // region R, lifetimes disjoint: reuse scratch (F0..F2) -> {Phi [N][N][2], B [N][N][2]} (F5..B1)
   // -> dbar [N][N][3] (B3..B4)
   static constexpr int R = yv + N * N;
-  // COMPACT (the 7-waves/SIMD proposal instantiation): Phi stays in registers (F5 -> B1), B alone
-  // in R, and F2's pair-patch scratch holds new - old differences [32][12] instead of the four parts
-  // [64][12]: 5.6 KB per wave for N2 (28 waves/CU fit the 160 KB)
   static constexpr int ph = R;
-  static constexpr int mx = COMPACT ? R : R + N * N * 2;
+  static constexpr int mx = R + N * N * 2;
   static constexpr int dbar = R;
-  static constexpr int R_n = COMPACT ? cmax(cmax(2 * N * N, 3 * N * N), 4 + 32 * 12)
-                                     : cmax(cmax(4 * N * N, 3 * N * N), 4 + 64 * 12);
+  static constexpr int R_n = cmax(cmax(4 * N * N, 3 * N * N), 4 + 64 * 12);
   // the walker's pivot record [2N+2] (proposals; [3N+2] walker launches) lives in the g2 region during F5: the g2
   // values are dead after F4 and their adjoints are written from B2 on
   static constexpr int pv = g2;
@@ -134,7 +115,7 @@ struct SmemRev {
   // FWDREG (proposals): F2's records of the moved electron's pairs for B3, [2][2][16][4]: (pair
   // (pi, o) | pair (o, pi)) x (layer 1 | layer 2) x o x 4 -- 16-byte rows at a 16-byte stride, so
   // that both the writes (lane o) and B3's reads (o = the pair's other electron) spread over the banks
-  static constexpr bool hand = FWDREG && kB3Handover;
+  static constexpr bool hand = FWDREG;
   static constexpr int th = (jdo + (FWDREG ? 64 : 0) + 3) / 4 * 4;
   static constexpr int end = hand ? th + 2 * 2 * 16 * 4 : jdo + (FWDREG ? 64 : 0);
   static constexpr int bytes = ((end * (int)sizeof(T)) + 15) & ~15;
@@ -215,15 +196,6 @@ __device__ __forceinline__ void pair_values(const T d[3], cptr<T> P, T out[3][4]
 template <typename T> __device__ __forceinline__ T class4_sum(T x) {
   x += dpp<0x124>(x);
   x += dpp<0x128>(x);
-#ifdef AQ_PERMLANE_SUM
-  if constexpr (sizeof(T) == 4) {
-    // across the rows on the VALU (gfx950 row swaps; the same additions as the xor shuffles)
-    const auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-    x = __uint_as_float(a[0]) + __uint_as_float(a[1]);
-    const auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-    return __uint_as_float(b[0]) + __uint_as_float(b[1]);
-  }
-#endif
   x += __shfl_xor(x, 16);
   x += __shfl_xor(x, 32);
   return x;
@@ -293,11 +265,6 @@ __device__ __forceinline__ void ld_vec(cptr<T> p, T* out) {
     }
   }
 }
-#ifndef AQ_NO_XLANE
-constexpr bool kXLane = true;    // F4 / B2 read the lane-order weight blocks in 16-byte loads
-#else
-constexpr bool kXLane = false;
-#endif
 
 // Barrier of a one-configuration wave: LDS traffic of one wave is processed in order, so a
 // wavefront-scope fence (a compiler barrier, no s_waitcnt) orders its cross-lane LDS accesses.
@@ -499,8 +466,8 @@ __global__ __launch_bounds__(64 * MOVED_WPB) void k_moved_value(KArgs ka) {
 #ifndef AQ_PREP_WAVES
 #define AQ_PREP_WAVES 4
 #endif
-template <typename T, int N, int A, bool PREP, bool PROP, bool PW7 = false> struct RevWaves {
-  static constexpr int value = PW7 ? 7 : (PREP ? (sizeof(T) == 4 ? AQ_PREP_WAVES : 2) : ((sizeof(T) == 4 && N == 14 && A == 2) ? (PROP ? AQ_PROP_WAVES : 4) : 1));
+template <typename T, int N, int A, bool PREP, bool PROP> struct RevWaves {
+  static constexpr int value = PREP ? (sizeof(T) == 4 ? AQ_PREP_WAVES : 2) : ((sizeof(T) == 4 && N == 14 && A == 2) ? (PROP ? AQ_PROP_WAVES : 4) : 1);
 };
 
 // PREP = false: value + gradient (Metropolis walker launches and single-electron proposal / ECP
@@ -525,15 +492,11 @@ template <typename T, int N, int A, bool PREP, bool PROP, bool PW7 = false> stru
 template <typename T, bool PROP, bool PREP = false> struct RevWpb {
   static constexpr int value = sizeof(T) != 4 ? 1 : (PROP ? AQ_PROP_WPB : (PREP ? 1 : AQ_WALK_WPB));
 };
-#ifdef AQ_WAVE_SYNC
-#define AQ_SYNC() wave_sync()
-#else
 #define AQ_SYNC()                                   \
   do {                                              \
     if constexpr (WPB > 1) wave_sync();             \
     else __syncthreads();                           \
   } while (0)
-#endif
 
 // One ordered pair (k, i) of B3 (walker_rev's pair adjoints): forward values (fresh) or the pair's
 // record tcache (pt_rec of the two layers' tanh outputs t1, t2), then the adjoints back through the two double layers to d = x_i - x_k, into dbar
@@ -593,7 +556,7 @@ __device__ __forceinline__ void b3_pair_adjoint(cptr<T> P, const T* xs, const T*
   for (int f = 0; f < 4; ++f) pb2[f] = g2b[((2 * 2 + G) * N + i) * 4 + f];
   T z2[4];
 #pragma unroll
-  for (int o = 0; o < 4; ++o) z2[o] = kPtFactor ? pb2[o] * t2[o] : pb2[o] * RSQ2 * (T(1) - t2[o] * t2[o]);
+  for (int o = 0; o < 4; ++o) z2[o] = pb2[o] * t2[o];
 #pragma unroll
   for (int m = 0; m < 4; ++m) {
     T s = g2b[((1 * 2 + G) * N + i) * 4 + m] + pb2[m] * RSQ2;
@@ -603,7 +566,7 @@ __device__ __forceinline__ void b3_pair_adjoint(cptr<T> P, const T* xs, const T*
   }
   T z1[4];
 #pragma unroll
-  for (int o = 0; o < 4; ++o) z1[o] = kPtFactor ? pb1[o] * t1[o] : pb1[o] * RSQ2 * (T(1) - t1[o] * t1[o]);
+  for (int o = 0; o < 4; ++o) z1[o] = pb1[o] * t1[o];
 #pragma unroll
   for (int m = 0; m < 4; ++m) {
     T s = g2b[((0 * 2 + G) * N + i) * 4 + m] + pb1[m] * RSQ2;
@@ -643,9 +606,6 @@ __device__ __forceinline__ void walker_draws(const __attribute__((address_space(
   }
 }
 
-// PW7 (proposals only, -DAQ_PW7 builds: measured slower, shape.hip): the small-batch instantiation, compiled for 7 waves/SIMD with the COMPACT
-// LDS layout, so that the B N proposals of a strong-scaling rank (512 N2 walkers: 7,168 waves) run
-// in one round instead of 1.4 (shape.hip chooses it by batch size)
 // PH (PREP only): the adjoint pass of the PHASE -- seeded by Im d log det / dH instead of Re, so
 // that the LapCache's node weights, feature adjoints and pair-local curvature are those of
 // theta = arg psi (the complex_output=True kinetic energy, hamiltonian.py:110-130)
@@ -653,21 +613,18 @@ __device__ __forceinline__ void walker_draws(const __attribute__((address_space(
 // per-electron stage F1 and everything after F2, wave 1 the pair stream F2 (its walker-cache rows,
 // the column sums g2, J_ee) at the same time; wave 1 hands g2 and J_ee over through LDS at one
 // workgroup barrier and exits.  F1 and F2 depend on the positions only (nn.py:106-153).
-template <typename T, int N, int A, bool PREP = false, bool PROP = false, bool PW7 = false, bool PH = false,
-          bool SPL = false>
-__global__ __attribute__((amdgpu_flat_work_group_size(1, 64 * (SPL ? 2 : RevWpb<T, PROP, PREP>::value)))) __attribute__((amdgpu_waves_per_eu(RevWaves<T, N, A, PREP, PROP, PW7>::value))) void
+template <typename T, int N, int A, bool PREP = false, bool PROP = false, bool PH = false, bool SPL = false>
+__global__ __attribute__((amdgpu_flat_work_group_size(1, 64 * (SPL ? 2 : RevWpb<T, PROP, PREP>::value)))) __attribute__((amdgpu_waves_per_eu(RevWaves<T, N, A, PREP, PROP>::value))) void
 k_walker_rev(KArgs ka) {
-  static_assert(!PW7 || (PROP && !PREP), "PW7 is a proposal instantiation");
   static_assert(!PH || PREP, "PH is an adjoint-pass instantiation");
   static_assert(!SPL || (!PROP && !PREP), "SPL is a walker-launch instantiation");
   using Ly = Lay<N, A>;
-  constexpr bool fwd_reg = PROP && kFwdReg;
-  constexpr bool compact = PROP && PW7 && fwd_reg;
+  constexpr bool fwd_reg = PROP;
   // the lane-order weight blocks in F4 / B2: proposals only (round 4, interleaved A/B on one box:
   // proposal launch 216.3-219.0 -> 215.1-218.2 us; the same in the walker launch and the local
   // energy's adjoint pass measured +0.5 us and +7-11 us per launch, profiles/r04_s5_ab_xlane.txt)
-  constexpr bool xlane = PROP && kXLane;
-  using SM = SmemRev<T, N, A, fwd_reg, compact>;
+  constexpr bool xlane = PROP;
+  using SM = SmemRev<T, N, A, fwd_reg>;
   using LCc = LapCache<N, A>;
   constexpr int D0 = SM::D0;
   constexpr int WPB = SPL ? 2 : RevWpb<T, PROP, PREP>::value;
@@ -754,12 +711,7 @@ k_walker_rev(KArgs ka) {
   const bool reuse = !PREP && PROP;
   // PROP: F1's walker-cache blocks by LDS-DMA (round 6, interleaved A/B on one box, N2 4096 walkers,
   // µs per proposal launch: 220.7 / 221.4 -> 220.5 / 220.6, positions bitwise equal; 21 VALU and one
-  // VGPR fewer per wave; profiles/r06_s1_ab_f1_glds_slp.txt).  -DAQ_NO_F1_GLDS: VGPR-staged copies.
-#ifndef AQ_NO_F1_GLDS
-  constexpr bool f1_glds = PROP;
-#else
-  constexpr bool f1_glds = false;
-#endif
+  // VGPR fewer per wave than VGPR-staged copies; profiles/r06_s1_ab_f1_glds_slp.txt).
   // walker launch re-using its previous sweep's pivot order (F5; KArgs::pvok)
   const bool wfix = !PREP && !PROP && !isprop && ka.pvok != 0;
   T* Wc = (T*)ka.wcache + (size_t)(reuse ? pb : conf) * WC::size;
@@ -797,21 +749,10 @@ k_walker_rev(KArgs ka) {
         }
       }
     }
-    if constexpr (compact) {
-      // new - old: part 1 (3) sends its values to part 0 (2) sixteen lanes down; D[16 (part / 2) + o]
-#pragma unroll
-      for (int l = 0; l < 3; ++l)
-#pragma unroll
-        for (int f = 0; f < 4; ++f) {
-          const T w = __shfl_down(v[l][f], 16);
-          if ((part & 1) == 0) S[(16 * (part >> 1) + o) * 12 + l * 4 + f] = v[l][f] - w;
-        }
-    } else {
 #pragma unroll
     for (int l = 0; l < 3; ++l)
 #pragma unroll
       for (int f = 0; f < 4; ++f) S[lane * 12 + l * 4 + f] = v[l][f];
-    }
     if (part < 2 && o < N && o != pi) {
       if constexpr (!PROP) {
         cusp = P[Ly::jee_c + pi * N + o];
@@ -830,18 +771,13 @@ k_walker_rev(KArgs ka) {
   if (reuse) {
     // walker pb's cached stage and pair sums, electron pi's entries from k_moved_electron;
     // all loads issued before the first LDS store
-    constexpr int NY = (N * N + 63) / 64, NHh = (N * D0 + 63) / 64, NG = (3 * 2 * N * 4 + 63) / 64;
-    T ry[NY], rh[NHh], rg[NG];
-    // f1_glds: the walker's Yt, ae-feature and g2 blocks go global -> LDS by LDS-DMA (no VGPR
-    // staging, no per-element selection); the moved electron's rows are patched in after they land
-    T eyv = T(0), eh0 = T(0);
-    if constexpr (f1_glds) {
-      lds_dma<T>(Yv, Wc + WC::yv, N * N, lane);
-      lds_dma<T>(sm + SM::hl, Wc + WC::h0, N * D0, lane);
-      lds_dma<T>(g2, Wc + WC::g2, 3 * 2 * N * 4, lane);
-      eyv = Eq[EC::yv + (lane < N ? lane : N - 1)];
-      eh0 = Eq[EC::h0 + (lane < D0 ? lane : D0 - 1)];
-    }
+    // the walker's Yt, ae-feature and g2 blocks go global -> LDS by LDS-DMA (no VGPR staging, no
+    // per-element selection); the moved electron's rows are patched in after they land
+    lds_dma<T>(Yv, Wc + WC::yv, N * N, lane);
+    lds_dma<T>(sm + SM::hl, Wc + WC::h0, N * D0, lane);
+    lds_dma<T>(g2, Wc + WC::g2, 3 * 2 * N * 4, lane);
+    const T eyv = Eq[EC::yv + (lane < N ? lane : N - 1)];
+    const T eh0 = Eq[EC::h0 + (lane < D0 ? lane : D0 - 1)];
     // PROP: F0's positions too (walker pb's, the moved electron's proposed position from
     // k_moved_electron), so that every global load of F0/F1 is in flight before one barrier
     // Every load is issued unconditionally at a clamped, in-bounds index and the moved electron's
@@ -854,30 +790,6 @@ k_walker_rev(KArgs ka) {
       xm = Eq[EC::xp + (mvl ? lane - 3 * pi : 0)];
       jee_params(jc, ja);   // before the cache loads: F2's pair values wait for these only
       rsl = rowsrc[lane < N ? lane : N - 1];   // F5's slot table (after F4)
-    }
-    // unsigned offsets: the loads take the wave's base pointer in SGPRs plus a 32-bit lane offset
-    if constexpr (!f1_glds) {
-#pragma unroll
-    for (int t = 0; t < NY; ++t) {
-      const unsigned idx = lane + 64 * t;
-      const unsigned ix = idx < N * N ? idx : N * N - 1;
-      const unsigned r = ix / N;
-      const T a = Wc[WC::yv + ix], b = Eq[EC::yv + (ix - r * N)];
-      ry[t] = ((int)r == pi) ? b : a;
-    }
-#pragma unroll
-    for (int t = 0; t < NHh; ++t) {
-      const unsigned idx = lane + 64 * t;
-      const unsigned ix = idx < N * D0 ? idx : N * D0 - 1;
-      const unsigned e = ix / D0;
-      const T a = Wc[WC::h0 + ix], b = Eq[EC::h0 + (ix - e * D0)];
-      rh[t] = ((int)e == pi) ? b : a;
-    }
-#pragma unroll
-    for (int t = 0; t < NG; ++t) {
-      const int idx = lane + 64 * t;
-      rg[t] = Wc[WC::g2 + (idx < 3 * 2 * N * 4 ? idx : 3 * 2 * N * 4 - 1)];
-    }
     }
     {
       // one load per value from a selected address, masked to +0 by a bit and: a select between
@@ -907,22 +819,10 @@ k_walker_rev(KArgs ka) {
       AQ_SYNC();
       f2_pair_values(jc, ja);
     }
-    if constexpr (f1_glds) {
-      // the DMA'd blocks have landed (vmcnt counts LDS-DMA) before the moved electron's rows go over them
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      if (lane < N) Yv[pi * N + lane] = eyv;
-      if (lane < D0) sm[SM::hl + pi * D0 + lane] = eh0;
-    } else {
-#pragma unroll
-    for (int t = 0; t < NY; ++t)
-      if (lane + 64 * t < N * N) Yv[lane + 64 * t] = ry[t];
-#pragma unroll
-    for (int t = 0; t < NHh; ++t)
-      if (lane + 64 * t < N * D0) sm[SM::hl + lane + 64 * t] = rh[t];
-#pragma unroll
-    for (int t = 0; t < NG; ++t)
-      if (lane + 64 * t < 3 * 2 * N * 4) g2[lane + 64 * t] = rg[t];
-    }
+    // the DMA'd blocks have landed (vmcnt counts LDS-DMA) before the moved electron's rows go over them
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (lane < N) Yv[pi * N + lane] = eyv;
+    if (lane < D0) sm[SM::hl + pi * D0 + lane] = eh0;
   } else if (!SPL || wv == 0) {
     if (wfix) pvr = Wc[WC::pv + (lane < 3 * N + 2 ? lane : 3 * N + 1)];   // to LDS after F4, before F5's write
     ElecOut<T, A> eo;
@@ -985,7 +885,7 @@ k_walker_rev(KArgs ka) {
 #pragma unroll
           for (int f = 0; f < 4; ++f)
             g2[((l * 2 + Gp) * N + lane) * 4 + f] +=
-                (compact ? S[lane * 12 + l * 4 + f] : S[lane * 12 + l * 4 + f] - S[(16 + lane) * 12 + l * 4 + f]) * gw;
+                (S[lane * 12 + l * 4 + f] - S[(16 + lane) * 12 + l * 4 + f]) * gw;
       }
     } else if (lane < 40) {
       const int t = lane - 16;
@@ -996,7 +896,7 @@ k_walker_rev(KArgs ka) {
       // issued together instead of one dependent round trip per electron of the group
 #pragma unroll
       for (int k = 0; k < N; ++k) {
-        const T dv = compact ? S[(16 + k) * 12 + l * 4 + f] : S[(32 + k) * 12 + l * 4 + f] - S[(48 + k) * 12 + l * 4 + f];
+        const T dv = S[(32 + k) * 12 + l * 4 + f] - S[(48 + k) * 12 + l * 4 + f];
         acc += (k >= k0 && k < k1 && k != pi) ? dv : T(0);
       }
       g2[((l * 2 + G) * N + pi) * 4 + f] += acc * (G ? ginv1 : ginv0);
@@ -1151,11 +1051,7 @@ k_walker_rev(KArgs ka) {
   // accumulator layout): Phi = h^3 W + b on the matrix cores (F5 below).  Round 4, interleaved A/B
   // on one box (N2, 4096 walkers, µs per proposal launch): 224.2-225.1 -> 219.1-221.9, the
   // 16 orbital-weight VGPRs of the VALU form replaced by 4 (profiles/r04_s2_ab_mfma.txt)
-#ifndef AQ_NO_PHI_MFMA
   constexpr bool phi_mfma = PROP && sizeof(T) == 4 && (N + 3) / 4 == 4 && NH == 4;
-#else
-  constexpr bool phi_mfma = false;
-#endif
   // PROP: F5's orbital-weight column (lane column ccl of the spin-stacked [W_up; W_down] and both
   // biases), issued during F4's last layer so that F5 finds it loaded
   using V2o = typename Pair<T>::type;
@@ -1179,7 +1075,6 @@ k_walker_rev(KArgs ka) {
     for (int s = 0; s < 2; ++s) obs[s] = pair_make<T>(wcol[Ly::orb_b + s * N * 2], wcol[Ly::orb_b + s * N * 2 + 1]);
   };
   if (!AQ_ABL(2)) {
-#ifndef AQ_F4_NO_PRELOAD
   // this lane's layer weights (electron ic's conv weights and biases at unit ff, the single
   // layer's column ff), layer l + 1's issued before layer l's arithmetic so that their latency
   // overlaps it (left alone the compiler issues each layer's loads at their first use)
@@ -1234,38 +1129,17 @@ k_walker_rev(KArgs ka) {
     wsb[l] = sb[ff];
   };
   lw_load(0);
-#endif
 #pragma unroll
   for (int l = 0; l < 3; ++l) {
     const int d1 = l == 0 ? D0 : NH;
     const int DF = 3 * d1 + 8;
     const int Q = DF / 4;
     const int T4 = d1 / 4;
-    const cptr<T> convw = P + (l == 0 ? Ly::conv_w0 : (l == 1 ? Ly::conv_w1 : Ly::conv_w2)) + ic * DF;
-    const cptr<T> convb = P + (l == 0 ? Ly::conv_b0 : (l == 1 ? Ly::conv_b1 : Ly::conv_b2)) + ic * Q;
-    const cptr<T> sngw = P + (l == 0 ? Ly::sng_w0 : (l == 1 ? Ly::sng_w1 : Ly::sng_w2));
-    const cptr<T> sngb = P + (l == 0 ? Ly::sng_b0 : (l == 1 ? Ly::sng_b1 : Ly::sng_b2));
-#ifndef AQ_F4_NO_PRELOAD
-    (void)convw; (void)convb; (void)sngw; (void)sngb;  // the preloaded registers replace them
     if (l + 1 < 3) lw_load(l + 1);
-#ifndef AQ_F5_NO_PRELOAD
     if constexpr (PROP) {
       if (l == 2) orb_load();
     }
-#endif
     asm volatile("" ::: "memory");
-#define AQ_CW(q) wcv[l][q]
-#define AQ_CB(s4) wcb[l][s4]
-#define AQ_CR(q) wcb[l][q]
-#define AQ_SW(q) wsw[l][q]
-#define AQ_SB() wsb[l]
-#else
-#define AQ_CW(q) convw[4 * (q) + ff]
-#define AQ_CB(s4) convb[4 * (s4) + ff]
-#define AQ_CR(q) convb[q]
-#define AQ_SW(q) sngw[(q) * 4 + ff]
-#define AQ_SB() sngb[ff]
-#endif
     // conv output q = tanh(mean_4(f w) + b) over the input quad 4q..4q+3
     // (network_blocks.py:106-116): lane f of electron ic holds input 4q + f (h^l unit
     // 4t + f, a group mean of unit 4t + f, or a g2 unit f) and the quad adds the four
@@ -1295,12 +1169,10 @@ k_walker_rev(KArgs ka) {
         if (q < T4) F = hown[q];
         else if (q < 3 * T4) F = gown[(q - T4) / T4][(q - T4) % T4];
         else F = g2[((l * 2 + (q - 3 * T4)) * N + ic) * 4 + ff];
-        T z = F * AQ_CW(q);
-#ifndef AQ_NO_CONV_FOLD
+        T z = F * wcv[l][q];
         // opaque product: otherwise z + dpp(z) is contracted into fma(F, w, dpp(z)) and the DPP
         // move cannot fold into the add (v_mul + v_mov_dpp + v_fmac instead of v_mul + v_add_dpp)
         asm volatile("" : "+v"(z));
-#endif
         z += dpp<0xB1>(z);
         z += dpp<0x4E>(z);
         zc[q] = z;
@@ -1315,16 +1187,12 @@ k_walker_rev(KArgs ka) {
     for (int s4 = 0; s4 < SM::QM / 4; ++s4) {
       if (s4 < QF) {
         const int q0 = 4 * s4;
-#ifndef AQ_F4_BRANCH_SELECT
         // the four quad sums are complete before the selection: left to itself the compiler sinks
         // their last DPP add into divergent branches (exec-mask save/restore per output lane)
         T z0 = zc[q0], z1 = zc[q0 + 1], z2 = zc[q0 + 2], z3 = zc[q0 + 3];
         asm volatile("" : "+v"(z0), "+v"(z1), "+v"(z2), "+v"(z3));
         const T zs = (ff & 2) ? ((ff & 1) ? z3 : z2) : ((ff & 1) ? z1 : z0);
-#else
-        const T zs = ff == 0 ? zc[q0] : (ff == 1 ? zc[q0 + 1] : (ff == 2 ? zc[q0 + 2] : zc[q0 + 3]));
-#endif
-        const T c = f_tanh(zs * T(0.25) + AQ_CB(s4));
+        const T c = f_tanh(zs * T(0.25) + wcb[l][s4]);
         if constexpr (fwd_reg) cqr[l][s4] = c;
         else if (ilive) cqv[SM::cqo(l, ic) + q0 + ff] = c;
         cq[q0 + 0] = quad_bcast<0>(c);
@@ -1336,17 +1204,17 @@ k_walker_rev(KArgs ka) {
 #pragma unroll
     for (int q = 0; q < SM::QM; ++q) {
       if (q >= 4 * QF && q < Q) {
-        cq[q] = f_tanh(zc[q] * T(0.25) + AQ_CR(q));
+        cq[q] = f_tanh(zc[q] * T(0.25) + wcb[l][q]);
         if constexpr (fwd_reg) cqr[l][QF + q - 4 * QF] = cq[q];
         else if (ilive && (q & 3) == ff) cqv[SM::cqo(l, ic) + q] = cq[q];
       }
     }
-    T z = AQ_SB(), z1 = T(0);   // even / odd q: two independent chains
+    T z = wsb[l], z1 = T(0);   // even / odd q: two independent chains
 #pragma unroll
     for (int q = 0; q < SM::QM; ++q)
       if (q < Q) {
-        if (q & 1) z1 += cq[q] * AQ_SW(q);
-        else z += cq[q] * AQ_SW(q);
+        if (q & 1) z1 += cq[q] * wsw[l][q];
+        else z += cq[q] * wsw[l][q];
       }
     z += z1;
     const T sval = f_tanh(z);
@@ -1354,11 +1222,6 @@ k_walker_rev(KArgs ka) {
     else if (ilive) sv[(l * N + ic) * 4 + ff] = sval;
     const T hin = l == 0 ? hl[ic * D0 + ff] : hreg;
     hreg = (d1 == NH) ? (hin + sval) * RSQ2 : sval;
-#undef AQ_CW
-#undef AQ_CB
-#undef AQ_CR
-#undef AQ_SW
-#undef AQ_SB
   }
   }
   if (ilive) hl[SM::hoff(3) + ic * 4 + ff] = hreg;
@@ -1410,16 +1273,10 @@ k_walker_rev(KArgs ka) {
   }
   if constexpr (!PROP) AQ_SYNC();   // PROP: one wave, the Gauss-Jordan below forms Phi itself
   T logdet, phr, phi;
-#ifndef AQ_NO_YBAR_REG
   constexpr bool ybar_reg = PROP;
-#else
-  constexpr bool ybar_reg = false;
-#endif
   // PROP: the Gauss-Jordan's register block, after it X = (P A)^{-1}: lane 16 rg + c holds
   // X[4 rg + t][c] = B[4 rg + t][rec[c]] in a2[t] (gj.h), kept for B1's Yt adjoint
   V2o a2[(N + 3) / 4];
-  // compact: Phi[rec[rg RW + t]][c] of lane 16 rg + c, kept for B1 / the fallback
-  V2o phr4[(N + 3) / 4];
   if (reuse) {
     // the walker's pivot order (partial pivoting rerun only if a pivot comes out small)
     bool bad = false;
@@ -1434,9 +1291,6 @@ k_walker_rev(KArgs ka) {
       const int ccl = cc < N ? cc : N - 1;
       // column ccl of the spin-stacked orbital weights [W_up; W_down] and both biases, loaded
       // once at compile-time offsets from one lane base
-#if defined(AQ_F5_NO_PRELOAD) || defined(AQ_F4_NO_PRELOAD)
-      orb_load();
-#endif
       const V2* w = ow;
       const V2* bsp = obs;
       const int* stab = (const int*)(sm + SM::st) + 4 * RW * rg;
@@ -1465,9 +1319,7 @@ k_walker_rev(KArgs ka) {
 #pragma unroll
         for (int t = 0; t < RW; ++t) {
           const bool ok = fl4[t] != 2 && cc < N;
-          if constexpr (compact) {
-            phr4[t] = pair_make<T>(pre[t], pim[t]);
-          } else if (ok) {
+          if (ok) {
             const int e = yo4[t] - SM::yv + cc;   // r N + c
             Ph[e * 2 + 0] = pre[t];
             Ph[e * 2 + 1] = pim[t];
@@ -1485,9 +1337,7 @@ k_walker_rev(KArgs ka) {
 #pragma unroll
         for (int f = 0; f < 4; ++f) acc = pair_fma<T>(sm[hd + f], w[4 + f], acc);
         const bool ok = fl != 2 && cc < N;
-        if constexpr (compact) {
-          phr4[t] = acc;
-        } else if (ok) {
+        if (ok) {
           const int e = yo - SM::yv + cc;   // r N + c
           Ph[e * 2 + 0] = pair_re<T>(acc);
           Ph[e * 2 + 1] = pair_im<T>(acc);
@@ -1499,13 +1349,9 @@ k_walker_rev(KArgs ka) {
       // dependencies, issued ahead of co-resident waves in their load/LDS-bound phases
       // (measured: 224.7-226.3 -> 221.1-221.6 us per N2 launch; F4 too, B3, or the F1 load issue
       // were neutral or worse)
-#ifndef AQ_NO_PRIO
       __builtin_amdgcn_s_setprio(1);
-#endif
       if (!AQ_ABL(4)) gj_fixed_regs<T, N>(a2, Mx, lane, rec, logdet, phr, phi, bad);
-#ifndef AQ_NO_PRIO
       __builtin_amdgcn_s_setprio(0);
-#endif
     } else
     if (!AQ_ABL(4)) gj_inverse_fixed<T, N>(Ph, Yv, Mx, lane, sm + SM::pv, logdet, phr, phi, bad);
 #ifdef AQ_ABLATE
@@ -1518,27 +1364,8 @@ k_walker_rev(KArgs ka) {
 #ifdef AQ_PHASE_MARK
       AQ_PH(10);   // tools/isa_phases.py: the rarely taken pivoted fallback, counted apart
 #endif
-      if constexpr (compact) {
-        // compact layout: no Phi block in LDS; the pivoted inverse reads Phi from the B block it
-        // then overwrites (gj_inverse loads its whole input before it writes)
-        wave_sync();
-        const int cc = lane & 15, rg = lane >> 4;
-        constexpr int RW = (N + 3) / 4;
-#pragma unroll
-        for (int t = 0; t < RW; ++t) {
-          const int i = rg * RW + t;
-          if (i < N && cc < N) {
-            const int r = (int)sm[SM::pv + i];
-            Mx[(r * N + cc) * 2] = pair_re<T>(phr4[t]);
-            Mx[(r * N + cc) * 2 + 1] = pair_im<T>(phr4[t]);
-          }
-        }
-        wave_sync();
-        gj_inverse<T, N>(Mx, Yv, Mx, lane, logdet, phr, phi);
-      } else {
-        gj_inverse<T, N>(Ph, Yv, Mx, lane, logdet, phr, phi);
-      }
-      if constexpr (ybar_reg && !compact) {
+      gj_inverse<T, N>(Ph, Yv, Mx, lane, logdet, phr, phi);
+      if constexpr (ybar_reg) {
         // the register block of B for B1, from the pivoted inverse (natural layout in Mx)
         wave_sync();
         const int cc = lane & 15, rg = lane >> 4;
@@ -1594,58 +1421,11 @@ k_walker_rev(KArgs ka) {
   // ------------------------------------------------------------------ B1 adjoints of H (= h^3) and Yt
   T* hbar = sm + SM::hbar;
   T* ybar = sm + SM::ybar;
-#ifndef AQ_PREP_NO_MFMA
   // fp32 adjoint pass of the local energy: Q_f on the matrix cores (below), B1 from its diagonal
   constexpr bool q_mfma = PREP && sizeof(T) == 4 && NH == 4;
-#else
-  constexpr bool q_mfma = false;
-#endif
-#ifdef AQ_B1_MFMA
-  // fp32 value + gradient (proposals and walker launches): B1's H adjoint on the matrix cores.
-  // Opt-in, measured slower (round 4, interleaved A/B on one box, N2 4096 walkers, µs per
-  // proposal launch: 230.2-233.7 with it against 219.1-221.9 without; the walker launch 50.0-50.3
-  // against 49.3-49.4; profiles/r04_s2_ab_mfma.txt): the proposal instantiation spills at the
-  // 5-wave budget (96 VGPRs + 16 B) and the eight dependent MFMAs serialise on one accumulator
-  constexpr bool b1_mfma = !PREP && sizeof(T) == 4 && NH == 4;
-#else
-  constexpr bool b1_mfma = false;
-#endif
-  if constexpr (b1_mfma) {
-    // dL/dH[r][f] = Re Q_f[r,r] = Re sum_c W_{s(r)}[f][c] G[c][r], G[c][r] = Yt[r][c] B[c][r]:
-    // the (8 x N)(N x N) product [W_up; W_down] G on v_mfma_f32_16x16x4f32 (Re = W_re G_re -
-    // W_im G_im, two MFMAs per K-step of four columns c = 4 k + t, k = lane >> 4); A[i = f + 4 s][k]
-    // = W_s[f][c] (rows 8..15 zero), B[k][j = r] = G[c][r] from B (LDS) and Yt; accumulator v of
-    // lane 16 s + r is row f = v of spin block s, kept for the rows r of spin s (nn.py:432-456)
-    if (!AQ_ABL(8)) {
-      typedef float v4f __attribute__((ext_vector_type(4)));
-      const int j = lane & 15, kq = lane >> 4;
-      const bool jok = j < N;
-      const int jr = jok ? j : N - 1;
-      const int si = (j >> 2) & 1, fi = j & 3;   // A row j = f + 4 s
-      const bool iok = j < 8;
-      v4f acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        const int c = 4 * kq + t;
-        const bool cok = c < N;
-        const int cl = cok ? c : N - 1;
-        const float wr = P[Ly::orb_w + ((si * 4 + fi) * N + cl) * 2];
-        const float wi = P[Ly::orb_w + ((si * 4 + fi) * N + cl) * 2 + 1];
-        const float ar = (iok && cok) ? wr : 0.f, ai = (iok && cok) ? -wi : 0.f;
-        const float y = Yv[jr * N + cl];
-        const bool gok = cok && jok;
-        const float gr = gok ? y * (float)Mx[(cl * N + jr) * 2] : 0.f;
-        const float gi = gok ? y * (float)Mx[(cl * N + jr) * 2 + 1] : 0.f;
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(ar, gr, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(ai, gi, acc, 0, 0, 0);
-      }
-      if (jok && kq == (j >= nup ? 1 : 0)) {
-        const int h = SM::hoff(3) + rowsrc[j] * 4;
-#pragma unroll
-        for (int v = 0; v < 4; ++v) hbar[h + v] = acc[v];
-      }
-    }
-  } else
+  // (the value + gradient instantiations keep B1's H adjoint on the VALU: on the matrix cores the
+  // proposal launch measured 230.2-233.7 us against 219.1-221.9, spilling at the 5-wave budget;
+  // profiles/r04_s2_ab_mfma.txt)
   if (!q_mfma && lane < 4 * N && !AQ_ABL(8)) {
     const int r = lane >> 2, f = lane & 3;
     const int sp = r < nup ? 0 : 1;
@@ -1743,25 +1523,6 @@ k_walker_rev(KArgs ka) {
     }
   }
   AQ_SYNC();   // ybar overwrites Yt
-  if constexpr (compact) {
-    // dL/dYt[r][c] = Re(B[c][r] Phi[r][c]) with Phi from F5's registers (lane 16 rg + c, slot
-    // rg RW + t, r = rec[slot]) and B from LDS
-    if (!AQ_ABL(8)) {
-      const int cc = lane & 15, rg = lane >> 4;
-      constexpr int RW = (N + 3) / 4;
-      if (cc < N) {
-#pragma unroll
-        for (int t = 0; t < RW; ++t) {
-          const int i = rg * RW + t;
-          if (i < N) {
-            const int r = (int)sm[SM::pv + i];
-            const int e = r * N + cc;
-            ybar[e] = Mx[(cc * N + r) * 2] * pair_re<T>(phr4[t]) - Mx[(cc * N + r) * 2 + 1] * pair_im<T>(phr4[t]);
-          }
-        }
-      }
-    }
-  } else
   if constexpr (ybar_reg) {
     // dL/dYt[r][c] = Re(B[c][r] Phi[r][c]) from the register block: B[c][r] = a2[t] of lane
     // 16 rg + cc with c = 4 rg + t, r = rec[cc] (no B reads, no per-element index division)
@@ -1797,31 +1558,8 @@ k_walker_rev(KArgs ka) {
   // ------------------------------------------------------------------ B2 back through the h-stream layers
   // lane map of F4: the adjoint of h^{l+1}[i][f] stays in a register.
   T* g2b = sm + SM::g2;    // forward g2 values are dead after F4: reuse for their adjoints
-#ifndef AQ_NO_PRIO
   if constexpr (PROP) __builtin_amdgcn_s_setprio(1);
-#endif
   if (!AQ_ABL(16)) {
-#ifdef AQ_B2_PRELOAD
-    // as in F4: this lane's layer weights (the single layer's rows of the conv outputs this lane
-    // forms, electron ic's conv weights at unit ff), layer l - 1's issued before layer l
-    T bsw[3][SM::QM / 4][4], bcw[3][SM::QM];
-    auto bw_load = [&](int l) {
-      const int d1 = l == 0 ? D0 : NH;
-      const int DF = 3 * d1 + 8;
-      const int Q = DF / 4;
-      const cptr<T> cw = P + (l == 0 ? Ly::conv_w0 : (l == 1 ? Ly::conv_w1 : Ly::conv_w2)) + ic * DF;
-      const cptr<T> sw = P + (l == 0 ? Ly::sng_w0 : (l == 1 ? Ly::sng_w1 : Ly::sng_w2));
-#pragma unroll
-      for (int s4 = 0; s4 < SM::QM / 4; ++s4)
-        if (s4 < Q / 4)
-#pragma unroll
-          for (int m = 0; m < 4; ++m) bsw[l][s4][m] = sw[(4 * s4 + ff) * 4 + m];
-#pragma unroll
-      for (int q = 0; q < SM::QM; ++q)
-        if (q < Q) bcw[l][q] = cw[4 * q + ff];
-    };
-    bw_load(2);
-#endif
     T hb = hbar[SM::hoff(3) + ic * 4 + ff];
 #pragma unroll
     for (int l = 2; l >= 0; --l) {
@@ -1831,10 +1569,6 @@ k_walker_rev(KArgs ka) {
       const int T4 = d1 / 4;
       const cptr<T> convw = P + (l == 0 ? Ly::conv_w0 : (l == 1 ? Ly::conv_w1 : Ly::conv_w2)) + ic * DF;
       const cptr<T> sngw = P + (l == 0 ? Ly::sng_w0 : (l == 1 ? Ly::sng_w1 : Ly::sng_w2));
-#ifdef AQ_B2_PRELOAD
-      if (l > 0) bw_load(l - 1);
-      asm volatile("" ::: "memory");
-#endif
       // single: s = tanh(c Ws + b), h_out = res(h_in, s)
       const T sval = fwd_reg ? svr[l] : sv[(l * N + ic) * 4 + ff];
       const T sb = (d1 == NH) ? hb * RSQ2 : hb;
@@ -1854,7 +1588,7 @@ k_walker_rev(KArgs ka) {
       // and DPP broadcasts it (as the forward tanh's); the Q mod 4 rest on every lane
       const int QF = Q / 4;
       T cg[SM::QM];
-      T bcw8[Ly::XQ];   // kXLane: this lane's conv weights (electron ic, unit ff), 2 sixteen-byte loads
+      T bcw8[Ly::XQ];   // xlane: this lane's conv weights (electron ic, unit ff), 2 sixteen-byte loads
       if constexpr (xlane) {
         if (l == 0) ld_use<T, Ly::XQ, Ly::Q0>(P + Ly::xcw(l) + (ic * 4 + ff) * Ly::XQ, bcw8);
         else ld_use<T, Ly::XQ, Ly::Q1>(P + Ly::xcw(l) + (ic * 4 + ff) * Ly::XQ, bcw8);
@@ -1865,15 +1599,11 @@ k_walker_rev(KArgs ka) {
         if (q < Q && (!full || (q & 3) == 0)) {
           const int qq = full ? q + ff : q;     // output this lane forms
           T cb = T(0);
-          T srow[4];   // kXLane: single-layer weight row qq, one sixteen-byte load
+          T srow[4];   // xlane: single-layer weight row qq, one sixteen-byte load
           if constexpr (xlane) ld_vec<T, 4>(P + Ly::xsr(l) + qq * 4, srow);
 #pragma unroll
           for (int m = 0; m < 4; ++m) {
-#ifdef AQ_B2_PRELOAD
-            cb += zq[m] * (full ? bsw[l][q / 4][m] : sngw[qq * 4 + m]);
-#else
             cb += zq[m] * (xlane ? srow[m] : sngw[qq * 4 + m]);
-#endif
           }
           const T c = fwd_reg ? cqr[l][full ? q / 4 : QF + q - 4 * QF] : cqv[SM::cqo(l, ic) + qq];
           const T g = cb * (T(1) - c * c) * T(0.25);
@@ -1901,11 +1631,7 @@ k_walker_rev(KArgs ka) {
       T fb[SM::QM];
 #pragma unroll
       for (int q = 0; q < SM::QM; ++q)
-#ifdef AQ_B2_PRELOAD
-        if (q < Q) fb[q] = cg[q] * bcw[l][q];
-#else
         if (q < Q) fb[q] = cg[q] * (xlane ? bcw8[q] : convw[4 * q + ff]);
-#endif
       // g2 adjoints (inputs 3 d1 + 4G + f), consumed by B3
       if (ilive) {   // pre-scaled by the group-mean weights 1/|G| of the pair sums
         g2b[((l * 2 + 0) * N + ic) * 4 + ff] = fb[3 * T4 + 0] * ginv0;
@@ -1931,9 +1657,7 @@ k_walker_rev(KArgs ka) {
     }
   }
   AQ_SYNC();
-#ifndef AQ_NO_PRIO
   if constexpr (PROP) __builtin_amdgcn_s_setprio(0);
-#endif
 
   if constexpr (PREP) {
     // ---------------------------------------------------------------- local-energy adjoint pass: tail
@@ -2094,20 +1818,16 @@ k_walker_rev(KArgs ka) {
 #pragma unroll
     for (int m = 0; m < D0; ++m) lv[N + m] = lb[m * st];
   };
-  // where the proposal path issues B4's Jacobian loads: 0 = before B3 (their latency overlaps all
-  // of B3), k = after B3's iteration k - 1.  Round 4: 1..3 leave the fp32 N2 proposal kernel at 95
-  // VGPRs and do not remove the spills of a 6-wave build (15-16 VGPRs): not the pressure point
-#ifndef AQ_LV_AT
-#define AQ_LV_AT 0
-#endif
-  constexpr int lv_at = (reuse && PROP) ? AQ_LV_AT : 0;
-  if (lv_at == 0) lv_load();
+  // issued before B3, so that their latency overlaps all of it.  Round 4: issuing them after one of
+  // B3's iterations instead leaves the fp32 N2 proposal kernel at 95 VGPRs and does not remove the
+  // spills of a 6-wave build (15-16 VGPRs): not the pressure point
+  lv_load();
   AQ_PH(6);
   // ------------------------------------------------------------------ B3 pair adjoints d(logpsi)/d(x_i - x_k)
   T* dbar = sm + SM::dbar;
   // Proposals from the walker cache: the 2(N-1) pairs of the moved electron pi come first
-  // (iteration 0) with the records F2 handed over (or recompute their forward values); every
-  // other pair takes its record from walker pb's cache.
+  // (iteration 0) with the records F2 handed over; every other pair takes its record from walker
+  // pb's cache.
   // one ordered pair (k, i): forward values (fresh) or the pair's record, then the
   // adjoints back through the two double layers to d = x_i - x_k
   auto pair_adjoint = [&](int k, int i, bool may_fresh, bool fresh, const T* tcache, T cusp, T al) {
@@ -2159,9 +1879,7 @@ k_walker_rev(KArgs ka) {
 #pragma unroll
     for (int u = 0; u < NIT; ++u) {
       const int it = lane + 64 * u;
-      const bool rc = !SM::hand && u == 0;   // without the handover iteration 0 recomputes pi's pairs
-      if (it < NPR) pair_adjoint(pk[u], pi2[u], rc, rc && it < M, tc[u], jc[u], ja[u]);
-      if (lv_at == u + 1) lv_load();
+      if (it < NPR) pair_adjoint(pk[u], pi2[u], false, false, tc[u], jc[u], ja[u]);
     }
   } else if (!reuse) {
     if (!PREP && !isprop && ka.wcache) {

@@ -15,7 +15,7 @@ import os
 import sys
 
 KERNELS = {
-    "proposal": "k_walker_rev<float, 14, 2, false, true",   # (a trailing PW7 template flag since round 4)
+    "proposal": "k_walker_rev<float, 14, 2, false, true",   # prefixes: the flags after PROP vary (a PW7 flag from round 4 until it was removed)
     "walker": "k_walker_rev<float, 14, 2, false, false",
     "prep": "k_walker_rev<float, 14, 2, true, false",
     "lap": "k_walker_lap<float, 14, 2",

@@ -13,7 +13,8 @@ import json
 import os
 import sys
 
-# side configuration -> (dominant kernel(s) whose per-launch counters the bench's roofline uses)
+# side configuration -> (dominant kernel(s) whose per-launch counters the bench's roofline uses);
+# the k_walker_rev entry is a prefix up to PREP, PROP (the trailing flags changed between rounds)
 SIDES = {
     "ecp_c": ["k_quad_value<float, 4, 1>"],
     "ecp_c2": ["k_quad_value<float, 8, 2>"],

@@ -48,7 +48,10 @@ def rows(path):
                 "lds_bytes": int(t["LDS_Block_Size"]), "scratch": int(t["Scratch_Size"])})
 
 
-KIND = {  # template pattern -> AIQMC_LDS_* kind (the launches that size their LDS at launch time)
+# template pattern -> AIQMC_LDS_* kind (the launches that size their LDS at launch time).  The
+# k_walker_rev patterns are prefixes up to PREP, PROP: the flags after them differ between the
+# committed profiles (PW7, PH, SPL) and the current kernel (PH, SPL)
+KIND = {
     r"k_walker_rev<(float|double), (\d+), (\d+), false, true,": "proposal",
     r"k_walker_rev<(float|double), (\d+), (\d+), false, false,": "walker",
     r"k_walker_rev<(float|double), (\d+), (\d+), true,": "adjoint",

@@ -11,7 +11,11 @@ at launch); profiles/summarize.py uses this table instead, plus the library's ow
 figures (aiqmc_debug_launch_lds).
 
 usage: python tools/isa_resources.py [lib.so] > resources.json   (library default: the in-tree one)
+       python tools/isa_resources.py --digest [lib.so]            SHA-256 of each code object's .text and
+           .rodata (kernel descriptors), labelled by its first kernel: what a refactor that must not
+           change the compiled code compares between two builds
 """
+import hashlib
 import json
 import os
 import re
@@ -105,5 +109,31 @@ def resources(lib=DEFAULT_LIB):
     return {d: dict(table[m], symbol=m) for m, d in zip(names, demangle(names))}
 
 
+def section_sha256(co_path, section):
+    with tempfile.NamedTemporaryFile() as f:
+        subprocess.run([f"{LLVM}/llvm-objcopy", "-O", "binary", f"--only-section={section}", co_path, f.name],
+                       check=True, capture_output=True)
+        return hashlib.sha256(open(f.name, "rb").read()).hexdigest()
+
+
+def digests(lib=DEFAULT_LIB):
+    """[(first kernel (demangled), kernels, .text sha256, .rodata sha256)] per code object, sorted."""
+    rows = []
+    for co in code_objects(lib):
+        names = sorted(kernel_notes(co))
+        with tempfile.NamedTemporaryFile(suffix=".co") as f:
+            f.write(co)
+            f.flush()
+            rows.append((demangle(names[:1])[0] if names else "(no kernels)", len(names),
+                         section_sha256(f.name, ".text"), section_sha256(f.name, ".rodata")))
+    return sorted(rows)
+
+
 if __name__ == "__main__":
-    print(json.dumps(resources(sys.argv[1] if len(sys.argv) > 1 else DEFAULT_LIB), indent=1))
+    args = [a for a in sys.argv[1:] if a != "--digest"]
+    lib = args[0] if args else DEFAULT_LIB
+    if "--digest" in sys.argv[1:]:
+        for name, n, text, rodata in digests(lib):
+            print(f"{text}  {rodata}  {n:3d} kernels  {name}")
+    else:
+        print(json.dumps(resources(lib), indent=1))

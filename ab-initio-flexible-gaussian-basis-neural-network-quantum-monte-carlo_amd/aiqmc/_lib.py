@@ -106,6 +106,9 @@ _SIGNATURES = {
     "aiqmc_dmc_tmoves": (_int, [_vp, _vp, _i32, _dbl, _i32, _vp, _vp, _vp, _u64, _u64, _vp, _vp]),
     "aiqmc_spin_squared": (_int, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     "aiqmc_dipole": (_int, [_vp, _vp, _i32, _vp, _vp]),
+    "aiqmc_space_warp": (_int, [_vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp]),
+    "aiqmc_corr_level": (_int, [_i32, _i32, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "aiqmc_corr_final": (_int, [_vp, _vp, _i32, _vp, _vp]),
     "aiqmc_profile_enable": (_int, [_vp, _i32]),
     "aiqmc_profile_read": (_int, [_vp, _i32, _p(_dbl), _p(_i64)]),
     "aiqmc_energy_stats": (_int, [_vp, _i32, _i64, _vp, _i32, _vp]),
@@ -335,6 +338,74 @@ def sr_gram(o_re: torch.Tensor, o_im: Optional[torch.Tensor] = None, center_re: 
     return out
 
 
+def _corr_args(logabs0, e0, logabs1, logjac, e1):
+    """The level inputs as contiguous tensors of one dtype and device: logabs0 / e0 [n],
+    logabs1 / logjac / e1 [M, n] (e0 / e1 may be None at level 1)."""
+    la1 = logabs1 if logabs1.dim() == 2 else logabs1.reshape(1, -1)
+    M, n = la1.shape
+    dt = la1.dtype if la1.dtype in (torch.float32, torch.float64) else torch.float64
+    fix = lambda t, shape: None if t is None else t.to(la1.device, dt).reshape(shape).contiguous()
+    return (fix(logabs0, (n,)), fix(e0, (n,)), fix(la1, (M, n)), fix(logjac, (M, n)), fix(e1, (M, n))), M, n
+
+
+def corr_level(level: int, logabs0: torch.Tensor, e0: Optional[torch.Tensor], logabs1: torch.Tensor,
+               logjac: torch.Tensor, e1: Optional[torch.Tensor], L1: Optional[torch.Tensor] = None,
+               L2: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """aiqmc_corr_level on this rank's walkers: logabs0 / e0 [n], logabs1 / logjac / e1 [M, n]
+    (float32 or float64), lw = 2 (logabs1 - logabs0) + logjac.  Returns float64
+    level 1 -> [M] max_b lw (combine ranks with MAX); level 2 -> [M, 5] = [n, sum e0, sum w,
+    sum w e1, sum w^2], w = exp(lw - L1) (SUM); level 3 -> [M, 2] = [sum d, sum d^2],
+    d = (w n / sum w)(e1 - E_m) - (e0 - E_0) from L1 and the summed L2 (SUM).
+    Device tensors run the kernels; host tensors take the same formulas in torch float64."""
+    if level not in (1, 2, 3):
+        raise ValueError("corr_level: level must be 1, 2 or 3")
+    if level >= 2 and (e0 is None or e1 is None or L1 is None):
+        raise ValueError("corr_level: levels 2 and 3 need e0, e1 and the combined L1")
+    if level == 3 and L2 is None:
+        raise ValueError("corr_level: level 3 needs the summed L2")
+    (a0, x0, a1, lj, x1), M, n = _corr_args(logabs0, e0, logabs1, logjac, e1)
+    if n == 0:
+        raise ValueError("corr_level: empty batch")
+    if a1.is_cuda:
+        dev = a1.device
+        out = torch.empty((M,) if level == 1 else (M, 5 if level == 2 else 2), dtype=torch.float64, device=dev)
+        l1 = None if L1 is None else L1.to(dev, torch.float64).contiguous()
+        l2 = None if L2 is None else L2.to(dev, torch.float64).contiguous()
+        with torch.cuda.device(dev):
+            check(load().aiqmc_corr_level(level, _dt(a1), n, M, _ptr(a0), _ptr(x0), _ptr(a1), _ptr(lj), _ptr(x1),
+                                          _ptr(l1), _ptr(l2), _ptr(out), _stream(dev)), "aiqmc_corr_level")
+        return out
+    lw = 2.0 * (a1.double() - a0.double()[None]) + lj.double()
+    if level == 1:
+        return lw.max(dim=1).values
+    w = torch.exp(lw - L1.double().reshape(M, 1))
+    x0, x1 = x0.double(), x1.double()
+    if level == 2:
+        cnt = torch.full((M,), float(n), dtype=torch.float64)
+        return torch.stack([cnt, x0.sum().expand(M), w.sum(1), (w * x1).sum(1), (w * w).sum(1)], dim=1)
+    l2 = L2.double().reshape(M, 5)
+    E0, Em, scale = l2[:, 1] / l2[:, 0], l2[:, 3] / l2[:, 2], l2[:, 0] / l2[:, 2]
+    d = (w * scale[:, None]) * (x1 - Em[:, None]) - (x0[None] - E0[:, None])
+    return torch.stack([d.sum(1), (d * d).sum(1)], dim=1)
+
+
+def corr_final(L2: torch.Tensor, L3: torch.Tensor) -> torch.Tensor:
+    """aiqmc_corr_final: [M, 5] = [E_0, E_m, E_m - E_0, err_m, ESS_m] (float64) from the summed
+    level vectors L2 [M, 5] and L3 [M, 2]; host tensors take the same formulas in torch."""
+    M = L2.shape[0]
+    if L2.is_cuda:
+        l2, l3 = L2.to(torch.float64).contiguous(), L3.to(L2.device, torch.float64).contiguous()
+        res = torch.empty(M, 5, dtype=torch.float64, device=L2.device)
+        with torch.cuda.device(L2.device):
+            check(load().aiqmc_corr_final(_ptr(l2), _ptr(l3), M, _ptr(res), _stream(L2.device)), "aiqmc_corr_final")
+        return res
+    l2, l3 = L2.double().reshape(M, 5), L3.double().reshape(M, 2)
+    n, sd, sd2 = l2[:, 0], l3[:, 0], l3[:, 1]
+    E0, Em = l2[:, 1] / n, l2[:, 3] / l2[:, 2]
+    err = torch.sqrt((sd2 - sd * sd / n) / (n * (n - 1.0)))
+    return torch.stack([E0, Em, Em - E0, err, l2[:, 2] * l2[:, 2] / l2[:, 4]], dim=1)
+
+
 def energy_stats_final(out: torch.Tensor) -> torch.Tensor:
     """aiqmc_energy_stats_final: out[4..5] = [mean, variance] from a summed out[0..3], in place."""
     check(load().aiqmc_energy_stats_final(_ptr(out), _stream(out.device)), "aiqmc_energy_stats_final")
@@ -504,6 +575,29 @@ class Context:
         with torch.cuda.device(self.device):
             check(self._lib.aiqmc_dipole(self._h, _ptr(p), B, _ptr(mu), _stream(self.device)), "aiqmc_dipole")
         return mu
+
+    # -- correlated sampling (aiqmc/correlatedsamples) ------------------------
+    def space_warp(self, pos: torch.Tensor, new_atoms):
+        """The space-warp transform of the walkers from this context's atoms to the geometries
+        new_atoms [M, A, 3] (aiqmc_space_warp): (newpos [M, B, 3N], logjac [M, B]) of the context
+        dtype, logjac = sum_i log|det J_i|."""
+        p = self._pos(pos)
+        B = p.shape[0]
+        na = torch.as_tensor(np.asarray(new_atoms.detach().cpu()) if isinstance(new_atoms, torch.Tensor) else
+                             np.asarray(new_atoms), dtype=torch.float64)
+        if na.dim() == 2:
+            na = na[None]
+        if na.dim() != 3 or tuple(na.shape[1:]) != (self.A, 3):
+            raise ValueError(f"new_atoms must be [M, {self.A}, 3], got {tuple(na.shape)}")
+        M = na.shape[0]
+        na = na.to(self.device).contiguous()
+        newpos = torch.empty(M, B, 3 * self.N, dtype=self.dtype, device=self.device)
+        logjac = torch.empty(M, B, dtype=self.dtype, device=self.device)
+        if M and B:
+            with torch.cuda.device(self.device):
+                check(self._lib.aiqmc_space_warp(self._h, _ptr(p), B, _ptr(na), M, _ptr(newpos), _ptr(logjac),
+                                                 _stream(self.device)), "aiqmc_space_warp")
+        return newpos, logjac
 
     def logpsi_grad(self, pos: torch.Tensor):
         p = self._pos(pos)

@@ -342,6 +342,50 @@ int aiqmc_dipole(aiqmc_ctx* ctx, const void* pos, int32_t B, void* mu, void* str
  * restores it).  A chunk holds whole walkers, at least one.  Results do not depend on it. */
 int aiqmc_debug_set_obs_chunk(aiqmc_ctx* ctx, int32_t nconf);
 
+/* Space-warp transform between nuclear geometries with its Jacobian (correlated sampling: the
+ * walkers of one run at the context's atoms R evaluated at M nearby geometries R'_m).  The warp is
+ * the reference's correlatedsamples/corrsamples.py:23-47 (Filippi-Umrigar), per electron r:
+ *   d_a = r - R_a, r_a = |d_a|, w_a = q_a / sum_b q_b, q_a = (r_min / r_a)^4  (= r_a^-4 / sum r_b^-4,
+ *   scaled so that nothing overflows; r_min = 0: 1/k on the k atoms at zero distance),
+ *   r' = r + sum_a w_a dR_a, dR_a = R'_a - R_a, evaluated as r + dR_n + sum_a w_a (dR_a - dR_n) with n
+ *   the nearest atom (sum_a w_a = 1; a rigid translation is reproduced exactly).
+ * logjac[m][b] = sum_i log|det J_i|, J_i[k][l] = delta_kl + sum_a dR_a[k] d_l w_a(r_i) with
+ * grad w_a = 4 w_a sum_{b != a} w_b (g_b - g_a), g_a = d_a / r_a^2 (0 for r_min = 0), the 3x3
+ * determinant in closed form, electrons added in ascending slot order.  This is the Jacobian
+ * that correlatedsamples/jacobianWeights.py:22-51 leaves unfinished ("to be continued"; its
+ * 1 - atoms per Cartesian component is not a derivative).  Nothing is clamped: a singular J_i
+ * gives -inf.  pos [B][3N], newpos [M][B][3N] and logjac [M][B] (may be NULL) are of the ctx
+ * dtype; new_atoms is a DEVICE double [M][A][3]; dR is formed in double, the rest in the ctx
+ * dtype.  One launch, no workspace; a (m, b) row depends on nothing else, so the results are the
+ * same bits from run to run and for any B, M or chunking.  B == 0 or M == 0 writes nothing.
+ * AIQMC_EINVAL for a null context, negative B or M, or null pos / new_atoms / newpos, before the
+ * GPU is touched.  Needs no parameters. */
+int aiqmc_space_warp(aiqmc_ctx* ctx, const void* pos, int32_t B, const double* new_atoms, int32_t M,
+                     void* newpos, void* logjac, void* stream);
+
+/* The reweighted energy-difference estimator of correlated sampling as three levels whose rank
+ * partials combine in one all-reduce each (context-free, as aiqmc_loss_level).  The walkers x_b
+ * are drawn from |psi_R|^2; for geometry m, with T_m the space warp,
+ *   lw_b = 2 (logabs1[m][b] - logabs0[b]) + logjac[m][b]     (logabs1 = log|psi_R'm(T_m x_b)|),
+ * the probability ratio the reference's driver replaces by |log psi_R - log psi_R'|^2 at the
+ * un-warped positions (VMC/VMC_energy_correlated_samples.py:184).  Inputs of `dtype`:
+ * logabs0 [n], e0 [n] (Re E_L at (x_b; R)), logabs1 / logjac / e1 [M][n] (e1 = Re E_L at
+ * (T_m x_b; R'_m)); L1, L2, out are device doubles.  One workgroup per geometry, sums in double
+ * in a fixed tree order, no atomics:
+ *   level 1  out[m]       = max_b lw_b                                        (ranks: MAX)
+ *   level 2  out[m][0..4] = [n, sum e0, sum w, sum w e1, sum w^2], w_b = exp(lw_b - L1[m])  (SUM)
+ *   level 3  out[m][0..1] = [sum d, sum d^2],
+ *            d_b = (w_b n / sum w)(e1_b - E_m) - (e0_b - E_0), from L1 and the summed L2      (SUM)
+ * e0 / e1 may be NULL at level 1.  NaN and inf propagate (the maximum too). */
+int aiqmc_corr_level(int32_t level, int32_t dtype, int64_t n, int32_t M, const void* logabs0, const void* e0,
+                     const void* logabs1, const void* logjac, const void* e1, const double* L1, const double* L2,
+                     double* out, void* stream);
+
+/* res[m][0..4] = [E_0, E_m, E_m - E_0, err_m, ESS_m] from the summed L2 [M][5] and L3 [M][2]:
+ * E_0 = sum e0 / n, E_m = sum w e1 / sum w, ESS_m = (sum w)^2 / sum w^2 and the delta-method error
+ * err_m = sqrt((sum d^2 - (sum d)^2 / n) / (n (n - 1))) (NaN for n = 1). */
+int aiqmc_corr_final(const double* L2, const double* L3, int32_t M, double* res, void* stream);
+
 /* Optional HIP-event timing of the hot kernels, recorded on the caller's
  * stream around each launch while enabled.  Slots: 0 = proposal
  * value+gradient launches of aiqmc_mc_step, 1 = walker gradient launches of

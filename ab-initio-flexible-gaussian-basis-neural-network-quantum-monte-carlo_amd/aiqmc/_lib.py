@@ -66,6 +66,39 @@ class AiqmcEcp(ctypes.Structure):
     ]
 
 
+class AiqmcDensityCfg(ctypes.Structure):
+    """aiqmc_density_cfg: a family with a zero count is absent."""
+    _fields_ = [
+        ("grid_lo", ctypes.c_double * 3),
+        ("grid_hi", ctypes.c_double * 3),
+        ("grid_n", ctypes.c_int32 * 3),
+        ("rad_max", ctypes.c_double),
+        ("rad_n", ctypes.c_int32),
+        ("pair_max", ctypes.c_double),
+        ("pair_n", ctypes.c_int32),
+    ]
+
+
+DENSITY_LDS_WORDS = 4096       # AIQMC_DENSITY_LDS_WORDS: privatisation limit of radial + pair
+DENSITY_MAX_BINS = 1 << 20     # AIQMC_DENSITY_MAX_BINS
+DENSITY_MAX_WORDS = 1 << 28    # AIQMC_DENSITY_MAX_WORDS
+DENSITY_FIELDS = ("total", "skipped", "grid", "grid_out", "radial", "radial_out", "pair", "pair_out")
+
+
+def density_cfg(grid=None, radial=None, pair=None) -> AiqmcDensityCfg:
+    """grid = (lo[3], hi[3], n[3]), radial = (r_max, n), pair = (r_max, n); None: absent."""
+    cfg = AiqmcDensityCfg()
+    if grid is not None:
+        lo, hi, n = grid
+        for d in range(3):
+            cfg.grid_lo[d], cfg.grid_hi[d], cfg.grid_n[d] = float(lo[d]), float(hi[d]), int(n[d])
+    if radial is not None:
+        cfg.rad_max, cfg.rad_n = float(radial[0]), int(radial[1])
+    if pair is not None:
+        cfg.pair_max, cfg.pair_n = float(pair[0]), int(pair[1])
+    return cfg
+
+
 _vp, _i32, _i64, _u64, _dbl = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64, ctypes.c_double
 _int, _str = ctypes.c_int, ctypes.c_char_p
 
@@ -106,6 +139,8 @@ _SIGNATURES = {
     "aiqmc_dmc_tmoves": (_int, [_vp, _vp, _i32, _dbl, _i32, _vp, _vp, _vp, _u64, _u64, _vp, _vp]),
     "aiqmc_spin_squared": (_int, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     "aiqmc_dipole": (_int, [_vp, _vp, _i32, _vp, _vp]),
+    "aiqmc_density_layout": (_int, [_vp, _p(AiqmcDensityCfg), _p(_i64), _p(_i64), _p(_i32)]),
+    "aiqmc_density_accumulate": (_int, [_vp, _p(AiqmcDensityCfg), _vp, _i32, _vp, _vp, _vp]),
     "aiqmc_space_warp": (_int, [_vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp]),
     "aiqmc_corr_level": (_int, [_i32, _i32, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "aiqmc_corr_final": (_int, [_vp, _vp, _i32, _vp, _vp]),
@@ -575,6 +610,41 @@ class Context:
         with torch.cuda.device(self.device):
             check(self._lib.aiqmc_dipole(self._h, _ptr(p), B, _ptr(mu), _stream(self.device)), "aiqmc_dipole")
         return mu
+
+    def density_layout(self, cfg: AiqmcDensityCfg) -> dict:
+        """aiqmc_density_layout (host only): {"offsets": {name: first word}, "sizes": {name: words},
+        "n_words", "privatised"} of the int64 accumulator for cfg (density_cfg) on this context;
+        names in DENSITY_FIELDS order.  privatised: radial + pair take the LDS path."""
+        off = (ctypes.c_int64 * 8)()
+        nw, priv = ctypes.c_int64(0), ctypes.c_int32(0)
+        check(self._lib.aiqmc_density_layout(self._h, ctypes.byref(cfg), off, ctypes.byref(nw), ctypes.byref(priv)),
+              "aiqmc_density_layout")
+        ends = list(off[1:]) + [nw.value]
+        return {"offsets": dict(zip(DENSITY_FIELDS, off)),
+                "sizes": {k: e - o for k, o, e in zip(DENSITY_FIELDS, off, ends)},
+                "n_words": nw.value, "privatised": bool(priv.value)}
+
+    def density_accumulate(self, pos: torch.Tensor, acc: torch.Tensor, cfg: AiqmcDensityCfg,
+                           weights: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """aiqmc_density_accumulate: bins the walkers pos [B, 3N] (weights [B] or None) into acc, a
+        contiguous int64 tensor of density_layout(cfg)["n_words"] words on this context's device
+        (zeroed by the caller before the first call), in place on the current stream."""
+        p = self._pos(pos)
+        B = p.shape[0]
+        n_words = self.density_layout(cfg)["n_words"]
+        if not (isinstance(acc, torch.Tensor) and acc.dtype == torch.int64 and acc.device == self.device
+                and acc.is_contiguous() and acc.numel() == n_words):
+            raise ValueError(f"density_accumulate: acc must be a contiguous int64 tensor of {n_words} words on "
+                             f"{self.device}")
+        w = None
+        if weights is not None:
+            w = torch.as_tensor(weights).to(self.device, self.dtype).contiguous().reshape(-1)
+            if w.numel() != B:
+                raise ValueError("weights must have one entry per walker")
+        with torch.cuda.device(self.device):
+            check(self._lib.aiqmc_density_accumulate(self._h, ctypes.byref(cfg), _ptr(p), B, _ptr(w), _ptr(acc),
+                                                     _stream(self.device)), "aiqmc_density_accumulate")
+        return acc
 
     # -- correlated sampling (aiqmc/correlatedsamples) ------------------------
     def space_warp(self, pos: torch.Tensor, new_atoms):

@@ -338,6 +338,56 @@ int aiqmc_spin_squared(aiqmc_ctx* ctx, const void* pos, int32_t B, void* s2_re, 
  * under an ECP). */
 int aiqmc_dipole(aiqmc_ctx* ctx, const void* pos, int32_t B, void* mu, void* stream);
 
+/* Electron density and pair-correlation histograms, accumulated on the device across sweeps.
+ * This is the DIAGONAL of the one-body density matrix (not ferminet/observables.py's
+ * make_density_matrix, whose orbital projection needs an SCF basis): it needs only the walkers.
+ * One call bins B walkers into the caller-owned device accumulator acc (int64 words, zeroed by
+ * the caller before the first call, then only added to).  Three optional families; a family with
+ * zero bins is absent together with its outside words:
+ *   grid    [2][nx][ny][nz]  spin-resolved density on the box [grid_lo, grid_hi)
+ *   radial  [2][A][rad_n]    distances to each of the context's atoms over [0, rad_max)
+ *   pair    [3][pair_n]      electron-electron distances over pairs i < j over [0, pair_max)
+ * Channels: grid / radial 0 = the up slots, 1 = the down slots of the context's spin tables
+ * (spin_up_indices / spin_down_indices, not position order); pair 0 = up-up, 1 = down-down,
+ * 2 = up-down.  Accumulator layout, offsets8 of aiqmc_density_layout in this order:
+ *   total[1] skipped[1] grid[2 nx ny nz] grid_out[2] radial[2 A rad_n] radial_out[2 A]
+ *   pair[3 pair_n] pair_out[3]
+ * Bin rule, the same for every axis, in the context dtype T: f = (x - lo) * inv_h with
+ * inv_h = n / (hi - lo) formed in double and rounded to T once (distances: f = r * inv_h); a sample
+ * is inside iff f >= 0 && f < n, its bin is (int)floor(f); everything else (NaN and infinite
+ * coordinates included) is tallied in the channel's word of the family's `_out` array (a grid
+ * sample is inside iff all three axes are).
+ * Fixed point: the words count in units of 2^-32.  A sample of a walker of weight w (weights: T[B]
+ * or NULL) adds llrint((double)w * 4294967296.0), exactly 1 << 32 without weights; `total`
+ * accumulates the walker weights in the same units.  A walker whose weight is negative, not
+ * finite or >= 2^31 adds nothing and is counted in the plain integer `skipped`.  Capacity: 2^31
+ * units of weight per word before the int64 overflows.  All updates are integer adds: the words
+ * are the same bits for any launch shape, any chunking of the batch, any walker order and any
+ * number of ranks (sum the words).
+ * radial + radial_out + pair + pair_out are privatised per workgroup in LDS when they hold at most
+ * AIQMC_DENSITY_LDS_WORDS words (*privatised = 1), and go to global atomics above that; the words
+ * do not depend on the path.  One launch on `stream`, no workspace.  Needs no parameters.
+ * AIQMC_EINVAL, before any device work, with a message naming the field: a null context or
+ * configuration, B < 0, a negative count or one above AIQMC_DENSITY_MAX_BINS, grid_hi <= grid_lo
+ * (or not finite) on a present grid, rad_max / pair_max not positive and finite when its count is
+ * non-zero, more than AIQMC_DENSITY_MAX_WORDS words, a null pos / acc with B > 0.  B == 0 is a
+ * no-op. */
+#define AIQMC_DENSITY_LDS_WORDS 4096          /* 32 KiB of LDS per workgroup */
+#define AIQMC_DENSITY_MAX_BINS (1 << 20)      /* per count: exact in float */
+#define AIQMC_DENSITY_MAX_WORDS (1 << 28)     /* 2 GiB accumulator */
+typedef struct aiqmc_density_cfg {
+  double grid_lo[3], grid_hi[3];
+  int32_t grid_n[3];             /* any n == 0: no grid */
+  double rad_max;
+  int32_t rad_n;                 /* 0: none */
+  double pair_max;
+  int32_t pair_n;                /* 0: none */
+} aiqmc_density_cfg;
+int aiqmc_density_layout(const aiqmc_ctx* ctx, const aiqmc_density_cfg* cfg, int64_t* offsets8, int64_t* n_words,
+                         int32_t* privatised);
+int aiqmc_density_accumulate(aiqmc_ctx* ctx, const aiqmc_density_cfg* cfg, const void* pos, int32_t B,
+                             const void* weights, int64_t* acc, void* stream);
+
 /* Diagnostics: configurations per value launch of aiqmc_spin_squared (default 4096; nconf <= 0
  * restores it).  A chunk holds whole walkers, at least one.  Results do not depend on it. */
 int aiqmc_debug_set_obs_chunk(aiqmc_ctx* ctx, int32_t nconf);

@@ -6,6 +6,7 @@ Module paths mirror the reference package (AIQMCrelease3):
   aiqmc.VMC.VMCmcstep              main_monte_carlo, walkers_update, limdrift
   aiqmc.observables                make_s2, make_dipole (the vendored ferminet/observables.py)
   aiqmc.correlatedsamples          corrsamples, jacobianWeights, estimator (energies of nearby geometries)
+  aiqmc.statistics                 make_blocking (no reference counterpart: error bars of serially correlated series)
   aiqmc.constants                  pmean / psum / all_gather over torch.distributed (RCCL)
   aiqmc.spin_indices               jastrow_indices_ee, spin_indices_h
   aiqmc.initial_electrons_positions.init   init_electrons

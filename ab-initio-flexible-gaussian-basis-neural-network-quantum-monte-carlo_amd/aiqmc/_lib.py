@@ -8,6 +8,7 @@ satisfies the library's NEEDED entry by SONAME).
 from __future__ import annotations
 
 import ctypes
+import functools
 import os
 from typing import Optional, Sequence
 
@@ -83,6 +84,8 @@ DENSITY_LDS_WORDS = 4096       # AIQMC_DENSITY_LDS_WORDS: privatisation limit of
 DENSITY_MAX_BINS = 1 << 20     # AIQMC_DENSITY_MAX_BINS
 DENSITY_MAX_WORDS = 1 << 28    # AIQMC_DENSITY_MAX_WORDS
 DENSITY_FIELDS = ("total", "skipped", "grid", "grid_out", "radial", "radial_out", "pair", "pair_out")
+BLOCKING_MAX_SERIES = 8        # AIQMC_BLOCKING_MAX_SERIES
+BLOCKING_MAX_LEVELS = 32       # AIQMC_BLOCKING_MAX_LEVELS
 
 
 def density_cfg(grid=None, radial=None, pair=None) -> AiqmcDensityCfg:
@@ -144,6 +147,8 @@ _SIGNATURES = {
     "aiqmc_space_warp": (_int, [_vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp]),
     "aiqmc_corr_level": (_int, [_i32, _i32, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "aiqmc_corr_final": (_int, [_vp, _vp, _i32, _vp, _vp]),
+    "aiqmc_blocking_layout": (_int, [_i64, _i32, _i32, _p(_i64), _p(_i64), _p(_i64)]),
+    "aiqmc_blocking_update": (_int, [_vp, _i32, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
     "aiqmc_profile_enable": (_int, [_vp, _i32]),
     "aiqmc_profile_read": (_int, [_vp, _i32, _p(_dbl), _p(_i64)]),
     "aiqmc_energy_stats": (_int, [_vp, _i32, _i64, _vp, _i32, _vp]),
@@ -439,6 +444,35 @@ def corr_final(L2: torch.Tensor, L3: torch.Tensor) -> torch.Tensor:
     E0, Em = l2[:, 1] / n, l2[:, 3] / l2[:, 2]
     err = torch.sqrt((sd2 - sd * sd / n) / (n * (n - 1.0)))
     return torch.stack([E0, Em, Em - E0, err, l2[:, 2] * l2[:, 2] / l2[:, 4]], dim=1)
+
+
+@functools.lru_cache(maxsize=64)
+def _blocking_words(B: int, K: int, L: int) -> tuple:
+    a, p, s = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
+    check(load().aiqmc_blocking_layout(B, K, L, ctypes.byref(a), ctypes.byref(p), ctypes.byref(s)),
+          "aiqmc_blocking_layout")
+    return a.value, p.value, s.value
+
+
+def blocking_layout(B: int, K: int, L: int) -> dict:
+    """aiqmc_blocking_layout (host only): the doubles of {"acc", "pend", "scratch"} for B chains,
+    K series and L levels."""
+    return dict(zip(("acc", "pend", "scratch"), _blocking_words(int(B), int(K), int(L))))
+
+
+def blocking_update(x: torch.Tensor, L: int, acc: torch.Tensor, pend: torch.Tensor, scratch: torch.Tensor) -> None:
+    """aiqmc_blocking_update: one sample x [K, B] (contiguous float32/float64 on the device) into
+    the float64 device buffers acc / pend / scratch of blocking_layout(B, K, L), in place on the
+    current stream (two launches, no host synchronisation)."""
+    if not (x.is_cuda and x.dim() == 2 and x.is_contiguous() and x.dtype in (torch.float32, torch.float64)):
+        raise ValueError("blocking_update: a contiguous [K, B] float32/float64 device tensor is required")
+    K, B = x.shape
+    for t, n, what in zip((acc, pend, scratch), _blocking_words(B, K, int(L)), ("acc", "pend", "scratch")):
+        if not (t.dtype == torch.float64 and t.device == x.device and t.is_contiguous() and t.numel() == n):
+            raise ValueError(f"blocking_update: {what} must be a contiguous float64 tensor of {n} words on {x.device}")
+    with torch.cuda.device(x.device):
+        check(load().aiqmc_blocking_update(_ptr(x), _dt(x), B, K, int(L), _ptr(acc), _ptr(pend), _ptr(scratch),
+                                           _stream(x.device)), "aiqmc_blocking_update")
 
 
 def energy_stats_final(out: torch.Tensor) -> torch.Tensor:

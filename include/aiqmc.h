@@ -436,6 +436,38 @@ int aiqmc_corr_level(int32_t level, int32_t dtype, int64_t n, int32_t M, const v
  * err_m = sqrt((sum d^2 - (sum d)^2 / n) / (n (n - 1))) (NaN for n = 1). */
 int aiqmc_corr_final(const double* L2, const double* L3, int32_t M, double* res, void* stream);
 
+/* Error bars for serially correlated series: the Flyvbjerg-Petersen blocking analysis in its
+ * online form, accumulated on the device across sweeps (context-free, as aiqmc_sr_gram).  A sample
+ * is one call's values x[K][B] (`dtype`): K series over the SAME B Markov chains in the same order
+ * at every call.  With t the number of samples taken so far (0-based index of this one):
+ *   v_0 = x - shift completes level 0;  for k = 0, 1, ..: stop if k + 1 == L; if bit k of t is set,
+ *   v_{k+1} = (pend[k+1] + v_k) / 2 completes level k + 1, go on; otherwise pend[k+1] = v_k, stop.
+ * A level-k block is thus the mean of 2^k consecutive samples of one chain, blocks aligned to the
+ * first sample; the top level L - 1 keeps receiving blocks of 2^(L-1) samples for ever.  Every level
+ * that completes adds, over all chains, n += B, S[i] += v_i, Q[i][j] += v_i v_j (i <= j).
+ * Buffers (device doubles, owned and zeroed by the caller before the first call; sizes from
+ * aiqmc_blocking_layout), M = 1 + K + K (K + 1) / 2:
+ *   acc      [t, shift[K], level 0 words[M], .., level L-1 words[M]], a level's words = [n, S[K],
+ *            Q upper triangle row-major]; t is a double (exact to 2^53), read AND incremented on
+ *            the device (the host never needs it); shift is written once by the caller after the
+ *            zeroing and keeps sum v^2 well conditioned
+ *   pend     [L][K][B], the blocks waiting for their partner (pend[0] is unused)
+ *   scratch  the partial sums of one call
+ * Nothing is clamped: NaN and inf propagate into exactly the levels they reach.  All arithmetic is
+ * fp64; fp32 samples are widened exactly.  No atomics: the chains are summed in fixed chunks of 256
+ * (a butterfly over each wave, then the four waves in order), the chunk partials in ascending
+ * chunk order by one workgroup of a second launch, so the words are a function of (B, samples)
+ * only, the same bits from run to run.  Two launches on `stream`, no host synchronisation.
+ * AIQMC_EINVAL, before any device work, with a message naming the field: a null x / acc / pend /
+ * scratch, B < 1 (or above 2^38), K outside 1..AIQMC_BLOCKING_MAX_SERIES, L outside
+ * 1..AIQMC_BLOCKING_MAX_LEVELS, an unknown dtype. */
+#define AIQMC_BLOCKING_MAX_SERIES 8
+#define AIQMC_BLOCKING_MAX_LEVELS 32
+int aiqmc_blocking_layout(int64_t B, int32_t K, int32_t L, int64_t* acc_words, int64_t* pend_words,
+                          int64_t* scratch_words);
+int aiqmc_blocking_update(const void* x, int32_t dtype, int64_t B, int32_t K, int32_t L, double* acc, double* pend,
+                          double* scratch, void* stream);
+
 /* Optional HIP-event timing of the hot kernels, recorded on the caller's
  * stream around each launch while enabled.  Slots: 0 = proposal
  * value+gradient launches of aiqmc_mc_step, 1 = walker gradient launches of

@@ -1,0 +1,375 @@
+"""aiqmc.statistics.make_blocking without a GPU: the torch path of the online Flyvbjerg-Petersen
+recurrence against direct numpy reblocking of the stored trace, known answers, the optimal-level
+rule, the ratio estimator, the checkpoint round trip, a 2-rank gloo reduction and the C ABI's
+argument checks.
+
+Two numpy references, neither using anything from the package (both also serve
+tests/test_gpu_blocking.py):
+
+``direct_reblock``  level k = the B floor(T / 2^k) means (numpy ``mean``) of 2^k consecutive samples.
+    Its blocks differ from the recurrence's by the rounding of a mean taken in another order, at
+    most about k u relative each (u = 2^-53), on top of the 2 n u sum |term| of the two summation
+    orders; with n <= 185 terms and k <= 5 here both stay below 1e-13 sum |term|, so the bound used
+    is TOL_DIRECT = 1e-12 sum |term| (the figure the recurrence was prototyped at).
+``pair_reblock``    the same blocks formed as (first + second) / 2 level by level: bit for bit the
+    recurrence's terms, so a sum may differ only by its order: 2 n u sum |term| (n terms).
+"""
+import ctypes
+import os
+import socket
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+from conftest import ROOT
+
+U = 2.0 ** -53
+TOL_DIRECT = 1e-12
+
+
+def _sums(blocks, B, K):
+    """Per-level sums of a list of block arrays [nb, K, B]: n [L], S [L, K], Q [L, K (K + 1) / 2]
+    and the sums of the absolute terms aS, aQ (numpy's summation order)."""
+    iu = np.triu_indices(K)
+    L = len(blocks)
+    out = {"n": np.zeros(L), "S": np.zeros((L, K)), "Q": np.zeros((L, iu[0].size)), "aS": np.zeros((L, K)),
+           "aQ": np.zeros((L, iu[0].size))}
+    for k, v in enumerate(blocks):
+        if v.shape[0] == 0:
+            continue
+        out["n"][k] = v.shape[0] * B
+        out["S"][k] = v.sum(axis=(0, 2))
+        out["aS"][k] = np.abs(v).sum(axis=(0, 2))
+        p = v[:, iu[0]] * v[:, iu[1]]
+        out["Q"][k] = p.sum(axis=(0, 2))
+        out["aQ"][k] = np.abs(p).sum(axis=(0, 2))
+    return out
+
+
+def direct_reblock(trace, shift, L):
+    """trace [T, K, B] -> _sums of the means of 2^k consecutive samples of x - shift, k < L."""
+    T, K, B = trace.shape
+    v = trace.astype(np.float64) - np.asarray(shift, dtype=np.float64)[None, :, None]
+    blocks = []
+    for k in range(L):
+        nb = T >> k
+        blocks.append(v[:nb << k].reshape(nb, 1 << k, K, B).mean(axis=1) if nb else np.zeros((0, K, B)))
+    return _sums(blocks, B, K), blocks
+
+
+def pair_reblock(trace, shift, L):
+    """The same blocks as (first + second) / 2 of the level below: the recurrence's own terms."""
+    T, K, B = trace.shape
+    v = trace.astype(np.float64) - np.asarray(shift, dtype=np.float64)[None, :, None]
+    blocks = []
+    for k in range(L):
+        blocks.append(v)
+        nb = v.shape[0] // 2
+        v = (v[0:2 * nb:2] + v[1:2 * nb:2]) / 2.0
+    return _sums(blocks, B, K), blocks
+
+
+def words_of(acc):
+    """(t, n [L], S [L, K], Q [L, Kq]) of an accumulator, numpy float64 on the host."""
+    a = acc.acc.detach().cpu().numpy()
+    w = a[1 + acc.K:].reshape(acc.L, acc.M)
+    return a[0], w[:, 0].copy(), w[:, 1:1 + acc.K].copy(), w[:, 1 + acc.K:].copy()
+
+
+def assert_words(acc, ref, T, factor, what=""):
+    """Counts and t exact; every S and Q word within factor * sum |term| of the reference, where
+    factor is a float or a callable of the word's term count."""
+    t, n, S, Q = words_of(acc)
+    assert t == T, (what, t)
+    np.testing.assert_array_equal(n, ref["n"], err_msg=what)
+    f = np.array([factor(x) if callable(factor) else factor for x in ref["n"]])[:, None]
+    for got, want, scale, name in ((S, ref["S"], ref["aS"], "S"), (Q, ref["Q"], ref["aQ"], "Q")):
+        err, bound = np.abs(got - want), f * scale
+        assert np.all(err <= bound), (what, name, float((err - bound).max()), float(err.max()))
+
+
+def order_bound(n):
+    """2 n u: two summation orders of the same n fp64 terms, as a factor of sum |term|."""
+    return 2.0 * n * U
+
+
+def feed(trace, L, shift=None, dtype=torch.float64, device="cpu"):
+    from aiqmc import statistics
+    T, K, B = trace.shape
+    acc = statistics.make_blocking(nseries=K, max_levels=L, shift=shift)
+    for t in range(T):
+        acc.update(torch.tensor(trace[t], dtype=dtype, device=device))
+    return acc
+
+
+def _trace(T, K, B, seed=1):
+    rng = np.random.default_rng(seed)
+    return rng.standard_normal((T, K, B)) + np.arange(1, K + 1)[None, :, None] * 3.0
+
+
+@pytest.mark.parametrize("shift", [None, (2.5, -1.0, 9.25)], ids=["zero_shift", "shift"])
+def test_recurrence_equals_direct_reblocking(shift):
+    T, K, B, L = 37, 3, 5, 8
+    tr = _trace(T, K, B)
+    acc = feed(tr, L, shift)
+    sh = np.zeros(K) if shift is None else np.asarray(shift)
+    ref, _ = direct_reblock(tr, sh, L)
+    assert ref["n"].tolist() == [B * (T >> k) for k in range(L)] and ref["n"][6] == 0
+    assert_words(acc, ref, T, TOL_DIRECT, "direct")
+    assert_words(acc, pair_reblock(tr, sh, L)[0], T, order_bound, "pair")
+    np.testing.assert_array_equal(acc.acc[1:1 + K].numpy(), sh)
+
+
+def test_level_cap_keeps_filling_the_top_level():
+    T, K, B, L = 21, 3, 5, 3
+    tr = _trace(T, K, B, seed=2)
+    acc = feed(tr, L)
+    ref, _ = direct_reblock(tr, np.zeros(K), L)
+    assert ref["n"].tolist() == [B * 21, B * 10, B * 5]
+    assert_words(acc, ref, T, TOL_DIRECT, "direct")
+    assert_words(acc, pair_reblock(tr, np.zeros(K), L)[0], T, order_bound, "pair")
+    # float32 samples are widened exactly
+    tr32 = tr.astype(np.float32)
+    assert_words(feed(tr32, L, dtype=torch.float32), pair_reblock(tr32.astype(np.float64), np.zeros(K), L)[0], T,
+                 order_bound, "fp32")
+
+
+def test_constant_and_alternating_series():
+    from aiqmc import statistics
+    T, B = 16, 3
+    const = statistics.reblock(np.full((T, B), 1.5), max_levels=8)
+    r = const.result()
+    assert r["n_blocks"].tolist() == [B * (T >> k) for k in range(5)]
+    assert r["block_size"].tolist() == [1, 2, 4, 8, 16]
+    np.testing.assert_array_equal(r["mean"].numpy(), 1.5)
+    np.testing.assert_array_equal(r["stderr"].numpy(), 0.0)
+    alt = statistics.reblock(np.tile(np.array([1.0, -1.0])[:, None], (T // 2, B)), max_levels=8)
+    r = alt.result()
+    n0 = B * T
+    # level 0: mean 0, sum x^2 = n, so var = n / (n - 1); every longer block is exactly zero
+    assert r["stderr"][0].item() == np.sqrt(n0 / (n0 - 1.0) / n0) == r["naive_stderr"]
+    assert r["stderr_err"][0].item() == r["stderr"][0].item() / np.sqrt(2.0 * (n0 - 1.0))
+    np.testing.assert_array_equal(r["stderr"][1:].numpy(), 0.0)
+    np.testing.assert_array_equal(r["mean"].numpy(), 0.0)
+
+
+def _ar1(phi=0.9, B=64, T=4096, burn=500):
+    eps = np.random.default_rng(0).standard_normal((T + burn, B))
+    x = np.empty_like(eps)
+    x[0] = eps[0]
+    for t in range(1, T + burn):
+        x[t] = phi * x[t - 1] + eps[t]
+    return x[burn:]
+
+
+def test_optimal_level_rule_and_ar1_anchor():
+    """The selected level equals a numpy restatement of the rule on directly reblocked data, and
+    on the AR(1) fixture stderr_opt lies within 15 % of the analytic error of the mean."""
+    from aiqmc import statistics
+    phi, B, T = 0.9, 64, 4096
+    x = _ar1(phi, B, T)
+    r = statistics.reblock(x).result()
+    err, nb = [], []
+    for k in range(13):
+        bl = x.reshape(T >> k, 1 << k, B).mean(axis=1).reshape(-1)
+        nb.append(bl.size)
+        err.append(np.sqrt(bl.var(ddof=1) / bl.size))
+    err, nb = np.array(err), np.array(nb, dtype=np.float64)
+    assert r["n_blocks"].tolist() == nb.tolist()
+    np.testing.assert_allclose(r["stderr"].numpy(), err, rtol=1e-9)
+    ok = [k for k in range(13) if nb[k] >= 2 and 2.0 ** (3 * k) > 2.0 * nb[0] * (err[k] / err[0]) ** 4]
+    assert r["converged"] and r["optimal_level"] == ok[0]
+    exact = np.sqrt((1 + phi) / ((1 - phi) * (1 - phi ** 2) * T * B))
+    ratio = r["stderr_opt"] / exact
+    print(f"AR(1): optimal level {r['optimal_level']}, stderr_opt / analytic = {ratio:.4f}, "
+          f"inefficiency {r['inefficiency']:.2f} (2 tau_int = {(1 + phi) / (1 - phi):.1f})")
+    assert 0.85 <= ratio <= 1.15
+    assert r["stderr_opt"] == r["stderr"][r["optimal_level"]].item()
+    assert r["inefficiency"] == (r["stderr_opt"] / r["naive_stderr"]) ** 2
+    # too short a trace for its correlation: no level qualifies
+    short = statistics.reblock(x[:8]).result()
+    assert short["optimal_level"] is None and not short["converged"] and np.isnan(short["stderr_opt"])
+
+
+def test_ratio_and_covariance_against_numpy():
+    from aiqmc import statistics
+    T, B, L = 24, 6, 6
+    rng = np.random.default_rng(4)
+    w = rng.uniform(0.5, 1.5, (T, B))
+    e = -10.0 + rng.standard_normal((T, B))
+    tr = np.stack([w * e, w], axis=1)
+    shift = (-10.0, 1.0)
+    acc = statistics.make_blocking(nseries=2, max_levels=L, shift=shift, names=("we", "w")).reblock(tr)
+    rr = acc.ratio("we", "w")
+    _, blocks = direct_reblock(tr, np.zeros(2), L)
+    for k in range(5):
+        a, b = blocks[k][:, 0].reshape(-1), blocks[k][:, 1].reshape(-1)
+        R = a.mean() / b.mean()
+        c = np.cov(a, b, ddof=1)
+        want = np.sqrt((c[0, 0] - 2 * R * c[0, 1] + R * R * c[1, 1]) / a.size) / abs(b.mean())
+        np.testing.assert_allclose(rr["ratio"][k].item(), R, rtol=1e-12)
+        np.testing.assert_allclose(rr["stderr"][k].item(), want, rtol=1e-9)
+        np.testing.assert_allclose(acc.covariance(k).numpy(), c, rtol=1e-9)
+    assert rr["n_blocks"].tolist() == [B * (T >> k) for k in range(5)]
+    np.testing.assert_allclose(acc.result("w")["mean"][0].item(), w.mean(), rtol=1e-13)
+    with pytest.raises(KeyError):
+        acc.result("nope")
+
+
+def test_state_dict_round_trip_mid_stream_is_bitwise(tmp_path):
+    from aiqmc import statistics
+    T, K, B, L = 29, 2, 7, 6
+    tr = _trace(T, K, B, seed=5)
+    whole = feed(tr, L, shift=(3.0, 6.0))
+    first = feed(tr[:13], L, shift=(3.0, 6.0))        # 13 = 0b1101: blocks pending at levels 1 and 2
+    torch.save(first.state_dict(), tmp_path / "b.pt")
+    sd = torch.load(tmp_path / "b.pt")
+    assert all(not v.is_cuda for v in sd.values() if isinstance(v, torch.Tensor))
+    resumed = statistics.make_blocking(nseries=K, max_levels=L)
+    resumed.load_state_dict(sd)
+    assert resumed.count == 13
+    for t in range(13, T):
+        resumed.update(torch.tensor(tr[t]))
+    assert torch.equal(resumed.acc, whole.acc) and torch.equal(resumed.pend, whole.pend)
+    with pytest.raises(ValueError, match="max_levels"):
+        statistics.make_blocking(nseries=K, max_levels=L + 1).load_state_dict(sd)
+    whole.reset()
+    assert whole.count == 0 and float(whole.acc[1 + K:].abs().sum()) == 0.0 and whole.acc[1:1 + K].tolist() == [3.0, 6.0]
+
+
+def test_update_argument_checks():
+    from aiqmc import statistics
+    acc = statistics.make_blocking(nseries=2)
+    with pytest.raises(TypeError, match=r"\.real and \.imag as two series"):
+        acc.update(torch.zeros(2, 4, dtype=torch.complex64))
+    with pytest.raises(TypeError, match="float32 or float64"):
+        acc.update(torch.zeros(2, 4, dtype=torch.int64))
+    with pytest.raises(ValueError, match=r"\[2, B\]"):
+        acc.update(torch.zeros(4))
+    acc.update(torch.zeros(2, 4))
+    with pytest.raises(ValueError, match="4 chains"):
+        acc.update(torch.zeros(2, 5))
+    with pytest.raises(ValueError, match=r"\[2, B\]"):
+        acc.update(torch.zeros(3, 4))
+    assert acc.count == 1
+    with pytest.raises(ValueError, match="nseries"):
+        statistics.make_blocking(nseries=9)
+    with pytest.raises(ValueError, match="max_levels"):
+        statistics.make_blocking(max_levels=33)
+    with pytest.raises(ValueError, match="shift"):
+        statistics.make_blocking(nseries=3, shift=(1.0, 2.0))
+    with pytest.raises(RuntimeError, match="update"):
+        statistics.make_blocking().result()
+
+
+_WORKER = r'''
+import os, sys
+sys.path.insert(0, sys.argv[1]); sys.path.insert(0, os.path.join(sys.argv[1], "ab-initio-flexible-gaussian-basis-neural-network-quantum-monte-carlo_amd"))
+sys.path.insert(0, os.path.join(sys.argv[1], "tests"))
+import numpy as np, torch, torch.distributed as dist
+rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
+dist.init_process_group("gloo")
+import test_blocking_host as T
+acc = T._two_rank_case(rank, world, extra=(sys.argv[3] == "unequal" and rank == 1))
+try:
+    acc.reduce()
+    np.save(os.path.join(sys.argv[2], f"acc_{rank}.npy"), acc.acc.numpy())
+except RuntimeError as e:
+    open(os.path.join(sys.argv[2], f"raised_{rank}.txt"), "w").write(str(e))
+dist.barrier()
+dist.destroy_process_group()
+'''
+
+_RANK_SHAPE = (21, 2, 10, 6)   # T, K, B over both ranks, L
+
+
+def _two_rank_case(rank, world, extra=False):
+    """This rank's half of the chains (all of them for world = 1); extra: one more sample."""
+    T, K, B, L = _RANK_SHAPE
+    tr = _trace(T + 1, K, B, seed=7)
+    n = B // world
+    acc = feed(tr[:T + (1 if extra else 0), :, rank * n:(rank + 1) * n], L, shift=(3.0, 6.0))
+    return acc
+
+
+def _run_ranks(tmp_path, mode):
+    world = 2
+    with socket.socket() as sk:
+        sk.bind(("127.0.0.1", 0))
+        port = sk.getsockname()[1]
+    procs = []
+    for r in range(world):
+        env = dict(os.environ, RANK=str(r), WORLD_SIZE=str(world), LOCAL_RANK=str(r), MASTER_ADDR="127.0.0.1",
+                   MASTER_PORT=str(port))
+        procs.append(subprocess.Popen([sys.executable, "-c", _WORKER, ROOT, str(tmp_path), mode], env=env))
+    for p in procs:
+        assert p.wait(timeout=240) == 0
+
+
+def test_two_rank_gloo_reduction_equals_one_process(tmp_path):
+    _run_ranks(tmp_path, "equal")
+    T, K, B, L = _RANK_SHAPE
+    one = _two_rank_case(0, 1)
+    one.reduce()                         # the identity in a single process
+    ref, _ = pair_reblock(_trace(T + 1, K, B, seed=7)[:T], (3.0, 6.0), L)
+    M = one.M
+    for r in range(2):
+        a = np.load(tmp_path / f"acc_{r}.npy")
+        assert a[0] == T and a[1:1 + K].tolist() == [3.0, 6.0]      # t and the shift are not summed
+        w, w1 = a[1 + K:].reshape(L, M), one.acc[1 + K:].numpy().reshape(L, M)
+        np.testing.assert_array_equal(w[:, 0], w1[:, 0])
+        np.testing.assert_array_equal(w[:, 0], ref["n"])
+        bound = order_bound(ref["n"])[:, None] * np.concatenate([ref["aS"], ref["aQ"]], axis=1)
+        assert np.all(np.abs(w[:, 1:] - w1[:, 1:]) <= bound)
+        assert np.all(np.abs(w[:, 1:] - np.concatenate([ref["S"], ref["Q"]], axis=1)) <= bound)
+
+
+def test_two_ranks_with_unequal_sample_counts_both_raise(tmp_path):
+    _run_ranks(tmp_path, "unequal")
+    for r in range(2):
+        msg = open(tmp_path / f"raised_{r}.txt").read()
+        assert "different sample counts" in msg and "21.0, 22.0" in msg
+        assert not os.path.exists(tmp_path / f"acc_{r}.npy")
+
+
+def test_c_abi_symbols_layout_and_einval_cases():
+    """Both symbols are in the header and exported; every refused argument returns AIQMC_EINVAL
+    with the field named, before any device work (the library loads without a GPU)."""
+    import re
+    from aiqmc import _lib
+    hdr = open(os.path.join(ROOT, "include", "aiqmc.h")).read()
+    lib = _lib.load()
+    for name in ("aiqmc_blocking_layout", "aiqmc_blocking_update"):
+        assert re.search(r"^int\s+" + name + r"\s*\(", hdr, re.M), name
+        assert name in _lib.EXPORTED_SYMBOLS and getattr(lib, name) is not None
+    for k, v in (("SERIES", _lib.BLOCKING_MAX_SERIES), ("LEVELS", _lib.BLOCKING_MAX_LEVELS)):
+        assert int(re.search(r"#define AIQMC_BLOCKING_MAX_" + k + r"\s+(\d+)", hdr).group(1)) == v
+    assert (_lib.BLOCKING_MAX_SERIES, _lib.BLOCKING_MAX_LEVELS) == (8, 32)
+    # layout: acc = 1 + K + L M, pend = L K B, scratch = ceil(B / 256) L (M - 1)
+    assert _lib.blocking_layout(1000, 3, 8) == {"acc": 1 + 3 + 8 * 10, "pend": 8 * 3 * 1000, "scratch": 4 * 8 * 9}
+    assert _lib.blocking_layout(256, 1, 1) == {"acc": 1 + 1 + 3, "pend": 256, "scratch": 2}
+    assert _lib.blocking_layout(257, 8, 32) == {"acc": 9 + 32 * 45, "pend": 32 * 8 * 257, "scratch": 2 * 32 * 44}
+    a, p, s = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+    out = (ctypes.byref(a), ctypes.byref(p), ctypes.byref(s))
+    for (B, K, L), field in (((0, 1, 8), "B"), ((-5, 1, 8), "B"), ((4, 0, 8), "K"), ((4, 9, 8), "K"), ((4, 1, 0), "L"),
+                             ((4, 1, 33), "L")):
+        assert lib.aiqmc_blocking_layout(B, K, L, *out) == -1
+        assert re.search(r"\b" + field + r"\b", _lib.last_error()), (field, _lib.last_error())
+        buf = (ctypes.c_double * 8)()
+        ptr = ctypes.cast(buf, ctypes.c_void_p)
+        assert lib.aiqmc_blocking_update(ptr, _lib.AIQMC_F64, B, K, L, ptr, ptr, ptr, None) == -1
+        assert re.search(r"\b" + field + r"\b", _lib.last_error()), (field, _lib.last_error())
+    assert lib.aiqmc_blocking_layout(4, 1, 8, None, ctypes.byref(p), ctypes.byref(s)) == -1
+    buf = (ctypes.c_double * 8)()
+    ptr = ctypes.cast(buf, ctypes.c_void_p)
+    for pos, field in ((0, "x"), (5, "acc"), (6, "pend"), (7, "scratch")):
+        args = [ptr, _lib.AIQMC_F64, 4, 1, 8, ptr, ptr, ptr, None]
+        args[pos] = None
+        assert lib.aiqmc_blocking_update(*args) == -1
+        assert re.search(r"null " + field + r"\b", _lib.last_error()), (field, _lib.last_error())
+    assert lib.aiqmc_blocking_update(ptr, 7, 4, 1, 8, ptr, ptr, ptr, None) == -1
+    assert "dtype" in _lib.last_error()
+    assert all(v == 0.0 for v in buf)

@@ -86,6 +86,8 @@ DENSITY_MAX_WORDS = 1 << 28    # AIQMC_DENSITY_MAX_WORDS
 DENSITY_FIELDS = ("total", "skipped", "grid", "grid_out", "radial", "radial_out", "pair", "pair_out")
 BLOCKING_MAX_SERIES = 8        # AIQMC_BLOCKING_MAX_SERIES
 BLOCKING_MAX_LEVELS = 32       # AIQMC_BLOCKING_MAX_LEVELS
+# rows of aiqmc_energy_components, in the order of the AIQMC_COMP_* macros (AIQMC_NCOMPONENTS = 8)
+COMPONENT_NAMES = ("total", "kinetic", "kinetic_grad", "v_ee", "v_en", "v_nn", "v_pp_local", "v_pp_nonlocal")
 
 
 def density_cfg(grid=None, radial=None, pair=None) -> AiqmcDensityCfg:
@@ -142,6 +144,7 @@ _SIGNATURES = {
     "aiqmc_dmc_tmoves": (_int, [_vp, _vp, _i32, _dbl, _i32, _vp, _vp, _vp, _u64, _u64, _vp, _vp]),
     "aiqmc_spin_squared": (_int, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     "aiqmc_dipole": (_int, [_vp, _vp, _i32, _vp, _vp]),
+    "aiqmc_energy_components": (_int, [_vp, _vp, _i32, _i32, _i32, _vp, _u64, _u64, _vp, _vp]),
     "aiqmc_density_layout": (_int, [_vp, _p(AiqmcDensityCfg), _p(_i64), _p(_i64), _p(_i32)]),
     "aiqmc_density_accumulate": (_int, [_vp, _p(AiqmcDensityCfg), _vp, _i32, _vp, _vp, _vp]),
     "aiqmc_space_warp": (_int, [_vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp]),
@@ -644,6 +647,28 @@ class Context:
         with torch.cuda.device(self.device):
             check(self._lib.aiqmc_dipole(self._h, _ptr(p), B, _ptr(mu), _stream(self.device)), "aiqmc_dipole")
         return mu
+
+    def energy_components(self, pos: torch.Tensor, complex_output: bool = False, rot: Optional[torch.Tensor] = None,
+                          seed: int = 0, offset: int = 0) -> torch.Tensor:
+        """What the local energy of each walker is made of (aiqmc_energy_components): a real tensor
+        [8, B], rows in the order of COMPONENT_NAMES; row 0 is the bits of local_energy /
+        local_energy_complex(...).real, under an ECP of local_energy_ecp(...).real with the same
+        rot / seed / offset (ignored without an ECP).  One sample for a make_blocking(nseries=8)
+        accumulator (aiqmc/Energy/components.py)."""
+        p = self._pos(pos)
+        B = p.shape[0]
+        out = torch.empty(len(COMPONENT_NAMES), B, dtype=self.dtype, device=self.device)
+        r = None
+        if rot is not None:
+            r = rot.to(self.device, self.dtype).contiguous()
+            if r.numel() != 9 * B:
+                raise ValueError("rot must be [B,3,3]")
+        mode = AIQMC_RNG_HOST if r is not None else AIQMC_RNG_PHILOX
+        with torch.cuda.device(self.device):
+            check(self._lib.aiqmc_energy_components(self._h, _ptr(p), B, 1 if complex_output else 0, mode, _ptr(r),
+                                                    ctypes.c_uint64(seed), ctypes.c_uint64(offset), _ptr(out),
+                                                    _stream(self.device)), "aiqmc_energy_components")
+        return out
 
     def density_layout(self, cfg: AiqmcDensityCfg) -> dict:
         """aiqmc_density_layout (host only): {"offsets": {name: first word}, "sizes": {name: words},

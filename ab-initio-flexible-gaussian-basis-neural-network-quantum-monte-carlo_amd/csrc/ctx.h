@@ -72,6 +72,9 @@ struct aiqmc_ctx {
   // configurations [n][3N], their log|psi| and phase [n], and the value launch's walker cache
   DevBuf d_obs_x, d_obs_lp, d_obs_ph, d_obs_wc;
   int obs_chunk = 4096;              // configurations per value launch (aiqmc_debug_set_obs_chunk)
+  // [counted] energy components (aiqmc_energy_components, components.hip), per batch: the
+  // all-electron E_L [B], an imaginary part [B], grad log|psi| [B][3N]
+  DevBuf d_comp;
   // optional per-kernel HIP-event timing (aiqmc_profile_*): slot -> recorded (start, stop) pairs
   bool prof = false;
   std::vector<hipEvent_t> ev_free;

@@ -338,6 +338,49 @@ int aiqmc_spin_squared(aiqmc_ctx* ctx, const void* pos, int32_t B, void* s2_re, 
  * under an ECP). */
 int aiqmc_dipole(aiqmc_ctx* ctx, const void* pos, int32_t B, void* mu, void* stream);
 
+/* What the local energy is made of: out[k][b] (AIQMC_NCOMPONENTS rows of B, ctx dtype, real), one
+ * sample x[K][B] for aiqmc_blocking_update (K = 8 = AIQMC_BLOCKING_MAX_SERIES):
+ *   AIQMC_COMP_TOTAL          Re E_L: written by aiqmc_local_energy (complex_output != 0:
+ *                             aiqmc_local_energy_complex), under an ECP by aiqmc_local_energy_ecp
+ *                             (aiqmc_local_energy_ecp_complex), called as they are -- their bits;
+ *                             rng_mode, rot, seed and offset are theirs and ignored without an ECP
+ *   AIQMC_COMP_KINETIC        T_L = the all-electron E_L of this context - (v_ee + v_en + v_nn)
+ *                             = -1/2 (lap log|psi| + |grad log|psi||^2), with complex_output plus the
+ *                             phase term 1/2 |grad theta|^2.  Under an ECP the all-electron entry is
+ *                             called as well as the ECP one.
+ *   AIQMC_COMP_KINETIC_GRAD   T_G = 1/2 sum |grad log|psi||^2 from the gradient of that launch.
+ *                             <T_G> = <T_L> over |psi|^2 for a wavefunction whose phase is piecewise
+ *                             constant (integration by parts); their gap is the standard check of
+ *                             the sample's equilibration and of the Laplacian.
+ *   AIQMC_COMP_V_EE           sum_{i<j} 1 / r_ij
+ *   AIQMC_COMP_V_EN           -sum_{i,a} Z_a / r_ia, Z the context charges (Z_eff under an ECP: part1
+ *                             of local_pp_energy, pseudopotential.py:111)
+ *   AIQMC_COMP_V_NN           sum_{a<b} Z_a Z_b / R_ab, summed on the host in double and rounded to the
+ *                             dtype: the same value for every walker
+ *   AIQMC_COMP_V_PP_LOCAL     sum_{i,a,k} c_ak r^(n_ak - 2) exp(-alpha_ak r^2) (pseudopotential.py:86-117
+ *                             without part1); 0 without aiqmc_set_ecp
+ *   AIQMC_COMP_V_PP_NONLOCAL  total - (kinetic + v_ee + v_en + v_nn + v_pp_local); 0 without an ECP
+ * One launch after the energy launches, a group of 16 lanes per walker; distances and terms in the
+ * ctx dtype, each walker summed in a fixed order (csrc/components.hip), no atomics: rows 3..6 of a
+ * walker depend on its coordinates alone and are the same bits for any B, batching or position in
+ * the batch.  Nothing is clamped: coincident particles give +-inf in that walker only, NaN
+ * propagates.  The scratch (one or two energy vectors, the gradient) is reserved at the first call.
+ * Non-zero, before any device work, with a message naming the field: a null context, parameters
+ * not set (AIQMC_ESTATE), B < 0, a null pos / out with B > 0, under an ECP an unknown rng_mode or
+ * AIQMC_RNG_HOST with a null rot.  B == 0 returns AIQMC_OK and writes nothing. */
+#define AIQMC_NCOMPONENTS 8
+#define AIQMC_COMP_TOTAL 0
+#define AIQMC_COMP_KINETIC 1
+#define AIQMC_COMP_KINETIC_GRAD 2
+#define AIQMC_COMP_V_EE 3
+#define AIQMC_COMP_V_EN 4
+#define AIQMC_COMP_V_NN 5
+#define AIQMC_COMP_V_PP_LOCAL 6
+#define AIQMC_COMP_V_PP_NONLOCAL 7
+int aiqmc_energy_components(aiqmc_ctx* ctx, const void* pos, int32_t B, int32_t complex_output,
+                            int32_t rng_mode, const void* rot, uint64_t seed, uint64_t offset,
+                            void* out /* [8][B], ctx dtype */, void* stream);
+
 /* Electron density and pair-correlation histograms, accumulated on the device across sweeps.
  * This is the DIAGONAL of the one-body density matrix (not ferminet/observables.py's
  * make_density_matrix, whose orbital projection needs an SCF basis): it needs only the walkers.

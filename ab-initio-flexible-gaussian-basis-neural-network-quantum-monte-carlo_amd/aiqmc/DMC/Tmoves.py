@@ -25,8 +25,9 @@ from typing import Union
 import numpy as np
 import torch
 
-from ..VMC.VMCmcstep import PhiloxKey
-from ..wavefunction_Ynlm.nn import AINetData
+from ..VMC.VMCmcstep import PhiloxKey, philox_key
+from ..utils.utils import np64
+from ..wavefunction_Ynlm.nn import AINetData, network_of
 
 
 @dataclasses.dataclass
@@ -36,46 +37,38 @@ class HostTmoveDraws:
     u_acc: torch.Tensor   # [B, N] acceptance uniforms (:216-217)
 
 
-def _np64(t):
-    return np.asarray(t.detach().cpu() if isinstance(t, torch.Tensor) else t, dtype=np.float64)
-
-
 def attach_nonlocal(ctx, natoms: int, list_l: int, rn_non_local, non_local_coes, non_local_exps):
-    """Give `ctx` the nonlocal tables unless its pp tables already hold the same ones."""
-    nl = tuple(_np64(t) for t in (rn_non_local, non_local_coes, non_local_exps))
+    """Give `ctx` the nonlocal tables unless its pp tables already hold the same ones (whatever
+    local part it holds then stays: a context shared with the pp local energy uploads nothing)."""
+    nl = tuple(np64(t) for t in (rn_non_local, non_local_coes, non_local_exps))
     if nl[0].reshape(natoms, -1).shape[1] % (int(list_l) + 1):
         raise ValueError("non-local tables must have list_l + 1 angular channels per atom")
-    tok = getattr(ctx, "_ecp_token", None)
-    want = (int(list_l),) + tuple(t.tobytes() for t in nl)
-    if tok is not None and (tok[0],) + tok[4:] == want:
+    have = ctx.ecp
+    if have is not None and have.list_l == int(list_l) and all(
+            a.tobytes() == b.tobytes() for a, b in zip((have.rn_non_local, have.non_local_coes,
+                                                        have.non_local_exps), nl)):
         return
     zero = np.zeros((natoms, 1))
     ctx.set_ecp(zero, zero, zero + 1.0, *nl, list_l=int(list_l))   # local part unused by T-moves
-    ctx._ecp_token = (int(list_l),) + tuple(t.tobytes() for t in (zero, zero, zero + 1.0)) + want[1:]
 
 
 def compute_tmoves(list_l: int, tstep: float, nelectrons: int, natoms: int, ndim: int, lognetwork,
                    Rn_non_local, Non_local_coes, Non_local_exps):
-    net = getattr(lognetwork, "_aiqmc_network", None)
-    if net is None:
-        raise TypeError("compute_tmoves: lognetwork must carry an aiqmc make_ai_net Network "
-                        "(use aiqmc.wavefunction_Ynlm.nn.make_log_network)")
+    net = network_of(lognetwork, "compute_tmoves")
     if ndim != 3 or nelectrons != net.nelectrons or natoms != net.natoms:
         raise ValueError("ndim / nelectrons / natoms do not match the network")
     if not tstep > 0:
         raise ValueError("tstep must be > 0")
 
     def calculate_ratio_weight_tmoves(data: AINetData, params, key: Union[int, PhiloxKey, HostTmoveDraws]):
-        pos = data.positions if isinstance(data.positions, torch.Tensor) else torch.as_tensor(
-            np.asarray(data.positions))
-        dtype = pos.dtype if pos.dtype in (torch.float32, torch.float64) else torch.float32
-        ctx = net.bind(params, data.atoms, dtype)
+        ctx, pos = net.bind_positions(params, data.positions, data.atoms)
+        dtype = ctx.dtype
         attach_nonlocal(ctx, natoms, list_l, Rn_non_local, Non_local_coes, Non_local_exps)
         work = pos.reshape(-1, 3 * nelectrons).to(ctx.device, dtype).contiguous().clone()
         if isinstance(key, HostTmoveDraws):
             acc = ctx.dmc_tmoves(work, tstep, rot=key.rot, u_sel=key.u_sel, u_acc=key.u_acc)
         else:
-            k = key if isinstance(key, PhiloxKey) else PhiloxKey(int(key or 0), 0)
+            k = philox_key(key or 0)
             acc = ctx.dmc_tmoves(work, tstep, seed=k.seed, offset=k.offset)
         return work.reshape(pos.shape), acc
 

@@ -10,15 +10,14 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from ..Energy.hamiltonian import _network_of
+from ..wavefunction_Ynlm.nn import kernel_dtype, network_of
 
 
 def branch(data, weights: torch.Tensor, key, network=None, params=None):
     u = float(key) if isinstance(key, float) else float(np.random.default_rng(int(key)).uniform())
-    net = _network_of(network) if network is not None else None
-    if net is None:
+    if network is None:
         raise TypeError("branch needs the aiqmc network (network=apply function) for its HIP context")
-    ctx = net.context(data.atoms, weights.dtype if weights.dtype in (torch.float32, torch.float64) else torch.float32)
+    ctx = network_of(network, "branch").context(data.atoms, kernel_dtype(weights))
     w, idx = ctx.dmc_branch(weights, u)
     return w, idx
 

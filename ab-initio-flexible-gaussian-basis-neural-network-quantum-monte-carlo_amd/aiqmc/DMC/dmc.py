@@ -25,8 +25,8 @@ import torch.distributed as dist
 
 from ..Energy import pphamiltonian
 from ..Energy.pphamiltonian import HostRotations
-from ..VMC.VMCmcstep import HostDraws, PhiloxKey
-from ..wavefunction_Ynlm.nn import AINetData
+from ..VMC.VMCmcstep import HostDraws, PhiloxKey, philox_key
+from ..wavefunction_Ynlm.nn import AINetData, network_of
 from .Tmoves import HostTmoveDraws, compute_tmoves
 from .drift_diffusion import propose_drift_diffusion
 
@@ -52,7 +52,7 @@ def dmc_propagate(signed_network, log_network, logabs_f, list_l: int, nelectrons
                                     rn_non_local=Rn_non_local, non_local_coes=Non_local_coes,
                                     non_local_exps=Non_local_exps, natoms=natoms, nelectrons=nelectrons, ndim=ndim,
                                     list_l=list_l)
-    net = signed_network._aiqmc_network
+    net = network_of(signed_network, "dmc_propagate")
     tm = compute_tmoves(list_l, tstep, nelectrons, natoms, ndim, signed_network, Rn_non_local, Non_local_coes,
                         Non_local_exps)
 
@@ -60,7 +60,7 @@ def dmc_propagate(signed_network, log_network, logabs_f, list_l: int, nelectrons
         if isinstance(key, HostDmcDraws):
             k_tm, k_eo, k_dd, k_en = key.tmoves, HostRotations(key.rot_old), key.drift, HostRotations(key.rot_new)
         else:
-            k = key if isinstance(key, PhiloxKey) else PhiloxKey(int(key), 0)
+            k = philox_key(key)
             k_tm, k_eo, k_dd, k_en = (PhiloxKey(k.seed + 3, k.offset), PhiloxKey(k.seed + 1, k.offset), k,
                                       PhiloxKey(k.seed + 2, k.offset))
         pos_t, _ = tm(data, params, k_tm)

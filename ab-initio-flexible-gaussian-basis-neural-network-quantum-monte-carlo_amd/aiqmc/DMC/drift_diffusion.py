@@ -8,25 +8,20 @@ the old and new positions.  key: PhiloxKey / int seed, or VMCmcstep.HostDraws (p
 """
 from __future__ import annotations
 
-import numpy as np
 import torch
 
-from ..VMC.VMCmcstep import HostDraws, PhiloxKey, diag_gauss2
-from ..wavefunction_Ynlm.nn import AINetData
+from ..VMC.VMCmcstep import HostDraws, PhiloxKey, diag_gauss2, philox_key
+from ..wavefunction_Ynlm.nn import AINetData, network_of
 
 
 def propose_drift_diffusion(logabs_f, tstep: float, ndim: int, nelectrons: int, batch_size: int):
-    net = getattr(logabs_f, "_aiqmc_network", None)
-    if net is None:
-        raise TypeError("propose_drift_diffusion: logabs_f must come from an aiqmc make_ai_net Network")
+    net = network_of(logabs_f, "propose_drift_diffusion")
     if ndim != 3 or nelectrons != net.nelectrons:
         raise ValueError("ndim/nelectrons do not match the network")
 
     def drift_diffusion(params, key, data: AINetData):
-        pos = data.positions if isinstance(data.positions, torch.Tensor) else torch.as_tensor(
-            np.asarray(data.positions))
-        dtype = pos.dtype if pos.dtype in (torch.float32, torch.float64) else torch.float32
-        ctx = net.bind(params, data.atoms, dtype)
+        ctx, pos = net.bind_positions(params, data.positions, data.atoms)
+        dtype = ctx.dtype
         p = pos.reshape(-1, 3 * nelectrons)
         if p.shape[0] != batch_size:
             raise ValueError(f"expected {batch_size} walkers per device, got {p.shape[0]}")
@@ -38,7 +33,7 @@ def propose_drift_diffusion(logabs_f, tstep: float, ndim: int, nelectrons: int, 
                                                  u=torch.as_tensor(key.u).reshape(1, batch_size, -1))
             newkey = key
         else:
-            k = key if isinstance(key, PhiloxKey) else PhiloxKey(int(key), 0)
+            k = philox_key(key)
             go, gn, td = ctx.dmc_drift_diffusion(work, tstep, seed=k.seed, offset=k.offset)
             newkey = PhiloxKey(k.seed, k.offset + 1)
         new = AINetData(positions=work.reshape(pos.shape), spins=data.spins, atoms=data.atoms, charges=data.charges)

@@ -218,7 +218,7 @@ def main(atoms, charges, spins, tstep: float, nelectrons: int, nsteps: int, nato
         pos = pos[rank * device_batch_size:(rank + 1) * device_batch_size]
     if pos.shape[0] != device_batch_size:
         raise ValueError(f"checkpoint holds {pos.shape[0]} walkers, expected {device_batch_size} per device")
-    dtype = pos.dtype if pos.dtype in (torch.float32, torch.float64) else torch.float32
+    dtype = nn.kernel_dtype(pos)
     data = nn.AINetData(positions=pos.to(dev, dtype).contiguous(), spins=data.spins, atoms=data.atoms,
                         charges=data.charges)
     key0 = PhiloxKey(seed + 7919 * rank, 0)
@@ -226,7 +226,7 @@ def main(atoms, charges, spins, tstep: float, nelectrons: int, nsteps: int, nato
     run = dmc_propagate(signed_network, log_network, signed_network, 2, nelectrons, natoms, ndim,
                         device_batch_size, tstep, nsteps, charges, spins, Rn_local, Local_coes, Local_exps,
                         Rn_non_local, Non_local_coes, Non_local_exps)
-    ctx = network.apply._aiqmc_network.bind(params, data.atoms, dtype)
+    ctx = nn.network_of(signed_network, "main_dmc").bind(params, data.atoms, dtype)
     rng = np.random.default_rng(seed + rank)
     out_dir = ckpt_restore_path or ckpt_save_path
     on_block = make_checkpoint_hook(out_dir, params, opt_state, save_frequency)

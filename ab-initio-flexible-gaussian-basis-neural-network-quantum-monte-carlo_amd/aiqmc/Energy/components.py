@@ -29,19 +29,15 @@ import numpy as np
 import torch
 
 from .. import statistics
-from .._lib import COMPONENT_NAMES
-from ..VMC.VMCmcstep import PhiloxKey
-from .hamiltonian import _network_of
+from .._lib import COMPONENT_NAMES, ECP_TABLE_NAMES
+from ..VMC.VMCmcstep import PhiloxKey, philox_key
+from ..utils.utils import np64
+from ..wavefunction_Ynlm.nn import as_positions, network_of
 from .pphamiltonian import HostRotations
 
 __all__ = ["COMPONENT_NAMES", "make_energy_components", "potential_terms", "summarize"]
 
-_PP_KEYS = ("rn_local", "local_coes", "local_exps", "rn_non_local", "non_local_coes", "non_local_exps")
 _POTENTIAL = ("v_ee", "v_en", "v_nn", "v_pp_local", "v_pp_nonlocal")
-
-
-def _np64(t) -> np.ndarray:
-    return np.asarray(t.detach().cpu() if isinstance(t, torch.Tensor) else t, dtype=np.float64)
 
 
 def make_energy_components(f, charges, nspins: Sequence[int], complex_output: bool = False, **pp_tables):
@@ -52,8 +48,8 @@ def make_energy_components(f, charges, nspins: Sequence[int], complex_output: bo
     all seven or none.  With them ``key`` selects the grid rotations as there -- a
     ``HostRotations``, a ``PhiloxKey`` or an int seed; without, it is ignored."""
     del nspins
-    net = _network_of(f)
-    c = _np64(charges)
+    net = network_of(f, "make_energy_components")
+    c = np64(charges)
     if c.shape != net.charges.shape or not np.allclose(c, net.charges):
         raise ValueError("make_energy_components charges differ from the network's charges")
     for k, want in (("natoms", net.natoms), ("nelectrons", net.nelectrons), ("ndim", 3)):
@@ -61,37 +57,30 @@ def make_energy_components(f, charges, nspins: Sequence[int], complex_output: bo
             raise ValueError(f"{k} does not match the network")
     pp_tables.pop("lognetwork", None)
     pp_tables.pop("use_scan", None)
-    unknown = set(pp_tables) - set(_PP_KEYS) - {"list_l"}
+    unknown = set(pp_tables) - set(ECP_TABLE_NAMES) - {"list_l"}
     if unknown:
         raise TypeError(f"make_energy_components: unknown keyword(s) {sorted(unknown)}")
-    token = None
+    tables = None
     if pp_tables:
-        missing = [k for k in _PP_KEYS + ("list_l",) if k not in pp_tables]
+        missing = [k for k in ECP_TABLE_NAMES + ("list_l",) if k not in pp_tables]
         if missing:
             raise ValueError(f"make_energy_components: pseudopotential tables need {missing} as well")
         list_l = int(pp_tables["list_l"])
-        tables = tuple(_np64(pp_tables[k]) for k in _PP_KEYS)
+        tables = tuple(np64(pp_tables[k]) for k in ECP_TABLE_NAMES)
         if tables[3].reshape(net.natoms, -1).shape[1] % (list_l + 1):
             raise ValueError("non-local tables must have list_l + 1 angular channels per atom")
-        token = (list_l,) + tuple(t.tobytes() for t in tables)
 
     def components(params, key: Union[int, PhiloxKey, HostRotations, None], data) -> torch.Tensor:
-        pos = data.positions if isinstance(data.positions, torch.Tensor) else torch.as_tensor(
-            np.asarray(data.positions))
-        dtype = pos.dtype if pos.dtype in (torch.float32, torch.float64) else torch.float32
-        ctx = net.bind(params, data.atoms, dtype)
-        have = getattr(ctx, "_ecp_token", None)
-        if token is None:
-            if have is not None:
+        ctx, pos = net.bind_positions(params, data.positions, data.atoms)
+        if tables is None:
+            if ctx.ecp is not None:
                 raise ValueError("this network's context carries pseudopotential tables: pass them to "
                                  "make_energy_components")
             return ctx.energy_components(pos, complex_output=complex_output)
-        if have != token:
-            ctx.set_ecp(*tables, list_l=list_l)
-            ctx._ecp_token = token
+        ctx.ensure_ecp(*tables, list_l=list_l)
         if isinstance(key, HostRotations):
             return ctx.energy_components(pos, complex_output=complex_output, rot=torch.as_tensor(key.rot))
-        k = key if isinstance(key, PhiloxKey) else PhiloxKey(int(key or 0), 0)
+        k = philox_key(key or 0)
         return ctx.energy_components(pos, complex_output=complex_output, seed=k.seed, offset=k.offset)
 
     components._aiqmc_network = net
@@ -107,10 +96,10 @@ def potential_terms(pos, atoms, charges, ecp_local=None) -> torch.Tensor:
       v_pp_local = sum_{i,a,k} c_ak r^(n_ak - 2) exp(-alpha_ak r^2), r^2 the sum of squares.
     ``ecp_local`` = (rn_local, local_coes, local_exps), each [A, KL]; None: v_pp_local = 0.
     Nothing is clamped: coincident particles give inf."""
-    x = pos if isinstance(pos, torch.Tensor) else torch.as_tensor(np.asarray(pos))
+    x = as_positions(pos)
     dt, dev = x.dtype, x.device
-    a64 = torch.as_tensor(_np64(atoms)).reshape(-1, 3)
-    z64 = torch.as_tensor(_np64(charges)).reshape(-1)
+    a64 = torch.as_tensor(np64(atoms)).reshape(-1, 3)
+    z64 = torch.as_tensor(np64(charges)).reshape(-1)
     A = a64.shape[0]
     x = x.reshape(-1, x.shape[-1] // 3, 3)
     N = x.shape[1]
@@ -130,7 +119,7 @@ def potential_terms(pos, atoms, charges, ecp_local=None) -> torch.Tensor:
     if ecp_local is None:
         v_pp = torch.zeros_like(v_ee)
     else:
-        rn, co, ex = (torch.as_tensor(_np64(t)).reshape(A, -1) for t in ecp_local)
+        rn, co, ex = (torch.as_tensor(np64(t)).reshape(A, -1) for t in ecp_local)
         n2 = (rn - 2.0).to(dev, dt)
         v_pp = (co.to(dev, dt) * r[..., None] ** n2 * torch.exp(-ex.to(dev, dt) * r2[..., None])).sum((-3, -2, -1))
     return torch.stack([v_ee, v_en, v_nn, v_pp])

@@ -18,6 +18,8 @@ from typing import Optional, Sequence, Tuple
 import numpy as np
 import torch
 
+from ..wavefunction_Ynlm.nn import network_of
+
 
 def potential_electron_electron(r_ee: torch.Tensor) -> torch.Tensor:
     """hamiltonian.py:177-187 (r_ee [..., N, N, 1])."""
@@ -46,26 +48,17 @@ def potential_energy(r_ae, r_ee, atoms, charges) -> torch.Tensor:
             + potential_nuclear_nuclear(charges, atoms))
 
 
-def _network_of(f):
-    net = getattr(f, "_aiqmc_network", None)
-    if net is None:
-        raise TypeError("local_energy: f must be the apply function of an aiqmc make_ai_net Network "
-                        "(the HIP local-energy kernel is specific to that ansatz)")
-    return net
-
-
 def local_kinetic_energy(f, use_scan: bool = False, complex_output: bool = True):
     """hamiltonian.py:77-132: returns ke(params, data) -> -1/2 (lap log|psi| + |grad log|psi||^2), or
     with complex_output (the reference's default here, :110-130) the complex
     -1/2 [lap log|psi| + i lap theta] - 1/2 |grad log|psi||^2 + 1/2 |grad theta|^2
     - i grad log|psi| . grad theta  (theta = arg psi; aiqmc_local_energy_complex)."""
     del use_scan
-    net = _network_of(f)
+    net = network_of(f, "local_kinetic_energy")
 
     def ke(params, data):
-        pos = data.positions if isinstance(data.positions, torch.Tensor) else torch.as_tensor(data.positions)
-        dtype = pos.dtype if pos.dtype in (torch.float32, torch.float64) else torch.float32
-        ctx = net.bind(params, data.atoms, dtype)
+        ctx, pos = net.bind_positions(params, data.positions, data.atoms)
+        dtype = ctx.dtype
         if complex_output:
             el = ctx.local_energy_complex(pos)
         else:
@@ -100,17 +93,14 @@ def local_energy(f, charges, nspins: Sequence[int], use_scan: bool = False, comp
     gradient from a second launch pair, aiqmc_local_energy_complex).
     """
     del nspins, use_scan
-    net = _network_of(f)
+    net = network_of(f, "local_energy")
     c = np.asarray(charges.detach().cpu() if isinstance(charges, torch.Tensor) else charges, dtype=np.float64)
     if c.shape != net.charges.shape or not np.allclose(c, net.charges):
         raise ValueError("local_energy charges differ from the network's charges")
 
     def _e_l(params, key, data) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
         del key
-        pos = data.positions if isinstance(data.positions, torch.Tensor) else torch.as_tensor(
-            np.asarray(data.positions))
-        dtype = pos.dtype if pos.dtype in (torch.float32, torch.float64) else torch.float32
-        ctx = net.bind(params, data.atoms, dtype)
+        ctx, pos = net.bind_positions(params, data.positions, data.atoms)
         if complex_output:
             el = ctx.local_energy_complex(pos)
         else:

@@ -25,8 +25,9 @@ from typing import Optional, Tuple, Union
 import numpy as np
 import torch
 
-from ..VMC.VMCmcstep import PhiloxKey
-from .hamiltonian import _network_of
+from ..VMC.VMCmcstep import PhiloxKey, philox_key
+from ..utils.utils import np64
+from ..wavefunction_Ynlm.nn import network_of
 
 
 @dataclasses.dataclass
@@ -40,33 +41,27 @@ def local_energy(f, lognetwork, charges, nspins, rn_local, local_coes, local_exp
     del nspins, use_scan, lognetwork
     if ndim != 3:
         raise NotImplementedError("ndim must be 3")
-    net = _network_of(f)
+    net = network_of(f, "pphamiltonian.local_energy")
     if natoms != net.natoms or nelectrons != net.nelectrons:
         raise ValueError("natoms / nelectrons do not match the network")
-    c = np.asarray(charges.detach().cpu() if isinstance(charges, torch.Tensor) else charges, dtype=np.float64)
+    c = np64(charges)
     if c.shape != net.charges.shape or not np.allclose(c, net.charges):
         raise ValueError("local_energy charges differ from the network's charges")
-    tables = tuple(np.asarray(t.detach().cpu() if isinstance(t, torch.Tensor) else t, dtype=np.float64)
-                   for t in (rn_local, local_coes, local_exps, rn_non_local, non_local_coes, non_local_exps))
+    tables = tuple(np64(t) for t in (rn_local, local_coes, local_exps, rn_non_local, non_local_coes,
+                                     non_local_exps))
     if tables[3].reshape(natoms, -1).shape[1] % (int(list_l) + 1):
         raise ValueError("non-local tables must have list_l + 1 angular channels per atom")
-    token = (int(list_l),) + tuple(t.tobytes() for t in tables)
 
     def _e_l(params, key: Union[int, PhiloxKey, HostRotations, None],
              data) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
-        pos = data.positions if isinstance(data.positions, torch.Tensor) else torch.as_tensor(
-            np.asarray(data.positions))
-        dtype = pos.dtype if pos.dtype in (torch.float32, torch.float64) else torch.float32
-        ctx = net.bind(params, data.atoms, dtype)
-        if getattr(ctx, "_ecp_token", None) != token:
-            ctx.set_ecp(*tables, list_l=int(list_l))
-            ctx._ecp_token = token
+        ctx, pos = net.bind_positions(params, data.positions, data.atoms)
+        ctx.ensure_ecp(*tables, list_l=int(list_l))
         # complex_output: the kinetic energy's phase terms (pphamiltonian.py:84-104 =
         # hamiltonian.py:110-130) added in the same call, from the log|psi| and theta launch pairs
         if isinstance(key, HostRotations):
             e = ctx.local_energy_ecp(pos, rot=torch.as_tensor(key.rot), complex_output=complex_output)
         else:
-            k = key if isinstance(key, PhiloxKey) else PhiloxKey(int(key or 0), 0)
+            k = philox_key(key or 0)
             e = ctx.local_energy_ecp(pos, seed=k.seed, offset=k.offset, complex_output=complex_output)
         return e.reshape(pos.shape[:-1]), None
 

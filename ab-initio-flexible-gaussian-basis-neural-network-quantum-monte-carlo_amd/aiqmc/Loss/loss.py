@@ -31,6 +31,7 @@ import numpy as np
 import torch
 
 from .. import constants
+from ..wavefunction_Ynlm.nn import network_of
 
 
 # diagnostics: False routes every step through the torch statistics path (the A/B of the fused
@@ -230,9 +231,7 @@ def make_loss(network, local_energy, clip_local_energy: float = 0.0, clip_from_m
               center_at_clipped_energy: bool = True, complex_output: bool = False):
     """loss.py:138-272.  `network` is the (log) network closure of the driver; the AIQMC
     network whose parameters are differentiated is taken from it or from `local_energy`."""
-    net = getattr(network, "_aiqmc_network", None) or getattr(local_energy, "_aiqmc_network", None)
-    if net is None:
-        raise TypeError("make_loss: local_energy must come from aiqmc.Energy (it carries the HIP network)")
+    net = network_of(network, None) or network_of(local_energy, "make_loss")
 
     def _energy(params, key, data):
         e_l, e_mat = local_energy(params, key, data)
@@ -261,13 +260,10 @@ def make_loss(network, local_energy, clip_local_energy: float = 0.0, clip_from_m
         rdt = e_l.real.dtype if cplx else e_l.dtype
         loss = torch.complex(st[0], st[1]).to(e_l.dtype) if cplx else st[0].to(rdt)
         variance = st[2].to(rdt)
-        pos = data.positions if isinstance(data.positions, torch.Tensor) else torch.as_tensor(
-            np.asarray(data.positions))
-        dtype = pos.dtype if pos.dtype in (torch.float32, torch.float64) else torch.float32
-        ctx = net.bind(params, data.atoms, dtype)
-        g = ctx.logpsi_param_grad(pos.reshape(B, -1), weights=w.to(ctx.device, dtype))
+        ctx, pos = net.bind_positions(params, data.positions, data.atoms)
+        g = ctx.logpsi_param_grad(pos.reshape(B, -1), weights=w.to(ctx.device, ctx.dtype))
         if phase:
-            g = g + ctx.phase_param_grad(pos.reshape(B, -1), weights=wp.to(ctx.device, dtype))
+            g = g + ctx.phase_param_grad(pos.reshape(B, -1), weights=wp.to(ctx.device, ctx.dtype))
         aux = AuxiliaryLossData(variance=variance, local_energy=e_l, clipped_energy=clipped, local_energy_mat=e_mat,
                                 imag_check=imag_check)
         return (loss, aux), g
@@ -302,18 +298,15 @@ def make_loss(network, local_energy, clip_local_energy: float = 0.0, clip_from_m
         else:
             center, diff = loss_c, e_c - loss_c
             aux_clipped = e_c                         # total_energy's clipped_energy = e_l
-        pos = data.positions if isinstance(data.positions, torch.Tensor) else torch.as_tensor(
-            np.asarray(data.positions))
-        dtype = pos.dtype if pos.dtype in (torch.float32, torch.float64) else torch.float32
-        ctx = net.bind(params, data.atoms, dtype)
+        ctx, pos = net.bind_positions(params, data.positions, data.atoms)
         B = diff.numel()
         scale = (2.0 if complex_output else 1.0) / B
         d_re = diff.real if torch.is_complex(diff) else diff
-        w = scale * d_re.reshape(-1).to(ctx.device, dtype)
+        w = scale * d_re.reshape(-1).to(ctx.device, ctx.dtype)
         g = ctx.logpsi_param_grad(pos.reshape(B, -1), weights=w)     # loss.py:256-265
         if cplx:
             cl = diff + aux_clipped
-            wp = scale * cl.imag.reshape(-1).to(ctx.device, dtype)
+            wp = scale * cl.imag.reshape(-1).to(ctx.device, ctx.dtype)
             g = g + ctx.phase_param_grad(pos.reshape(B, -1), weights=wp)
         aux = AuxiliaryLossData(variance=variance, local_energy=e_l, clipped_energy=center + diff,
                                 local_energy_mat=e_mat, imag_check=imag_check)
@@ -326,10 +319,7 @@ def make_loss(network, local_energy, clip_local_energy: float = 0.0, clip_from_m
         if not (constants._active() and _mean_centre and isinstance(e_l, torch.Tensor)):
             (loss, aux), g = _value_and_grad(params, data, e_l, e_mat)
             return (loss, aux), constants.pmean(g)
-        pos = data.positions if isinstance(data.positions, torch.Tensor) else torch.as_tensor(
-            np.asarray(data.positions))
-        dtype = pos.dtype if pos.dtype in (torch.float32, torch.float64) else torch.float32
-        ctx = net.bind(params, data.atoms, dtype)
+        ctx, pos = net.bind_positions(params, data.positions, data.atoms)
         B = e_l.numel()
         x = pos.reshape(B, -1)
 

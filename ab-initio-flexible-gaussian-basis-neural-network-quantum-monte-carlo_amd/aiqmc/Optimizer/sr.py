@@ -43,11 +43,10 @@ from __future__ import annotations
 import dataclasses
 from typing import Any, Callable, Optional
 
-import numpy as np
 import torch
 
 from .. import constants
-from ..wavefunction_Ynlm.nn import flatten_params_device
+from ..wavefunction_Ynlm.nn import as_positions, flatten_params_device, network_of
 
 # walkers per Jacobian block: a multiple of _lib.SR_CHUNK (asserted on the device path), so that a
 # batch cut into blocks sums in the same chunks as the batch in one piece
@@ -122,25 +121,16 @@ def fisher_from_jacobian(blocks: Callable[[], Any]):
     return S, n
 
 
-def _positions(data) -> torch.Tensor:
-    pos = data.positions if isinstance(data.positions, torch.Tensor) else torch.as_tensor(np.asarray(data.positions))
-    return pos
-
-
 def fisher(evaluate_loss, params, data, complex_output: bool):
     """(S [P, P] float64 on the device, n): the exact Fisher matrix of the wavefunction over the
     walkers ``data.positions`` of all ranks (module docstring).  ``evaluate_loss`` is the
     ``make_loss`` result; its network's kernels give the per-walker Jacobians.  An
     ``evaluate_loss.per_walker_jacobian(params, data, lo, hi) -> (o_re, o_im or None)`` attribute
     replaces them (another wavefunction, or synthetic Jacobians on host ranks)."""
-    pos = _positions(data)
+    pos = as_positions(data.positions)
     jac = getattr(evaluate_loss, "per_walker_jacobian", None)
     if jac is None:
-        net = getattr(evaluate_loss, "_aiqmc_network", None)
-        if net is None:
-            raise TypeError("fisher: evaluate_loss must come from aiqmc.Loss.loss.make_loss")
-        dtype = pos.dtype if pos.dtype in (torch.float32, torch.float64) else torch.float32
-        ctx = net.bind(params, data.atoms, dtype)
+        ctx, _ = network_of(evaluate_loss, "fisher").bind_positions(params, pos, data.atoms)
         x = pos.reshape(-1, pos.shape[-1])
 
         def jac(params_, data_, lo, hi):

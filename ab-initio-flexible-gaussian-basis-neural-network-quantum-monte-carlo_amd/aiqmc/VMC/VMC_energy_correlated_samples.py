@@ -70,7 +70,7 @@ def main(atoms, new_atoms, charges, spins, tstep: float, nelectrons: int, nsteps
         pos = pos[rank * device_batch_size:(rank + 1) * device_batch_size]
     if pos.shape[0] != device_batch_size:
         raise ValueError(f"checkpoint holds {pos.shape[0]} walkers, expected {device_batch_size} per device")
-    dtype = pos.dtype if pos.dtype in (torch.float32, torch.float64) else torch.float32
+    dtype = nn.kernel_dtype(pos)
     data = nn.AINetData(positions=pos.to(dev, dtype).contiguous(), spins=spins, atoms=atoms, charges=charges)
     key = VMCmcstep.PhiloxKey(seed + 7919 * rank, 0)
     data = mc_step(params, data, key)

@@ -20,10 +20,9 @@ from __future__ import annotations
 import dataclasses
 from typing import Union
 
-import numpy as np
 import torch
 
-from ..wavefunction_Ynlm.nn import AINetData
+from ..wavefunction_Ynlm.nn import AINetData, network_of
 
 
 def limdrift(g: torch.Tensor, tau: float, acyrus: float) -> torch.Tensor:
@@ -37,6 +36,12 @@ def limdrift(g: torch.Tensor, tau: float, acyrus: float) -> torch.Tensor:
 class PhiloxKey:
     seed: int = 0
     offset: int = 0
+
+
+def philox_key(key) -> PhiloxKey:
+    """A PhiloxKey as it is; an int seed as PhiloxKey(seed, 0).  None raises (int(None)): a closure
+    that accepts a missing key passes ``key or 0``."""
+    return key if isinstance(key, PhiloxKey) else PhiloxKey(int(key), 0)
 
 
 @dataclasses.dataclass
@@ -57,17 +62,13 @@ def diag_gauss2(gauss2: torch.Tensor, nelectrons: int) -> torch.Tensor:
 
 
 def main_monte_carlo(f, tstep: float, ndim: int, nelectrons: int, nsteps: int, batch_size: int):
-    net = getattr(f, "_aiqmc_network", None)
-    if net is None:
-        raise TypeError("main_monte_carlo: f must be the apply function of an aiqmc make_ai_net Network")
+    net = network_of(f, "main_monte_carlo")
     if ndim != 3 or nelectrons != net.nelectrons:
         raise ValueError("ndim/nelectrons do not match the network")
 
     def mc_step(params, data: AINetData, key: Union[int, PhiloxKey, HostDraws] = 0) -> AINetData:
-        pos = data.positions if isinstance(data.positions, torch.Tensor) else torch.as_tensor(
-            np.asarray(data.positions))
-        dtype = pos.dtype if pos.dtype in (torch.float32, torch.float64) else torch.float32
-        ctx = net.bind(params, data.atoms, dtype)
+        ctx, pos = net.bind_positions(params, data.positions, data.atoms)
+        dtype = ctx.dtype
         shape = pos.shape
         p = pos.reshape(-1, 3 * nelectrons)
         if p.shape[0] != batch_size:
@@ -79,7 +80,7 @@ def main_monte_carlo(f, tstep: float, ndim: int, nelectrons: int, nsteps: int, b
             ctx.mc_step(work, nsteps, tstep, gauss1=torch.as_tensor(key.gauss1), gauss2=g2,
                         u=torch.as_tensor(key.u))
         else:
-            k = key if isinstance(key, PhiloxKey) else PhiloxKey(int(key), 0)
+            k = philox_key(key)
             ctx.mc_step(work, nsteps, tstep, seed=k.seed, offset=k.offset)
         out = work.reshape(shape) if inplace else work.to(pos.device, pos.dtype).reshape(shape)
         return AINetData(positions=out, spins=data.spins, atoms=data.atoms, charges=data.charges)

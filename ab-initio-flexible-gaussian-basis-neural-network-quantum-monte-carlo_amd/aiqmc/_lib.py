@@ -7,6 +7,7 @@ satisfies the library's NEEDED entry by SONAME).
 """
 from __future__ import annotations
 
+import collections
 import ctypes
 import functools
 import os
@@ -17,6 +18,7 @@ import torch  # noqa: F401  (must precede loading the HIP library)
 
 AIQMC_F32 = 0
 AIQMC_F64 = 1
+AIQMC_EHIP = -3
 AIQMC_RNG_HOST = 0
 AIQMC_RNG_PHILOX = 1
 
@@ -65,6 +67,11 @@ class AiqmcEcp(ctypes.Structure):
         ("non_local_coes", ctypes.POINTER(ctypes.c_double)),
         ("non_local_exps", ctypes.POINTER(ctypes.c_double)),
     ]
+
+
+# the six pseudopotential tables in set_ecp's argument order; Context.ecp reports them with list_l
+ECP_TABLE_NAMES = ("rn_local", "local_coes", "local_exps", "rn_non_local", "non_local_coes", "non_local_exps")
+EcpView = collections.namedtuple("EcpView", ECP_TABLE_NAMES + ("list_l",))
 
 
 class AiqmcDensityCfg(ctypes.Structure):
@@ -226,6 +233,11 @@ def check(rc: int, what: str):
         raise RuntimeError(f"{what} failed ({rc}): {last_error()}")
 
 
+def _dt(t) -> int:
+    """AIQMC_F32 / AIQMC_F64 of a tensor or of a torch dtype."""
+    return AIQMC_F32 if getattr(t, "dtype", t) == torch.float32 else AIQMC_F64
+
+
 LDS_KINDS = ("proposal", "walker", "adjoint", "lap", "pgrad", "fwdlap")   # AIQMC_LDS_* order
 
 
@@ -235,8 +247,8 @@ def launch_lds(nelectrons: int, natoms: int, dtype=torch.float32) -> dict:
     out = {}
     for k, name in enumerate(LDS_KINDS):
         b, w = ctypes.c_int32(0), ctypes.c_int32(0)
-        check(lib.aiqmc_debug_launch_lds(int(nelectrons), int(natoms), AIQMC_F32 if dtype == torch.float32 else AIQMC_F64,
-                                         k, ctypes.byref(b), ctypes.byref(w)), "aiqmc_debug_launch_lds")
+        check(lib.aiqmc_debug_launch_lds(int(nelectrons), int(natoms), _dt(dtype), k, ctypes.byref(b),
+                                         ctypes.byref(w)), "aiqmc_debug_launch_lds")
         out[name] = {"dyn_lds_bytes_per_wg": b.value, "waves_per_wg": w.value}
     return out
 
@@ -261,8 +273,7 @@ def energy_stats(e_l: torch.Tensor, finalize: bool = True) -> torch.Tensor:
         raise ValueError("energy_stats: a float32/float64 device tensor is required")
     e = e_l.contiguous().reshape(-1)
     out = torch.empty(6, dtype=torch.float64, device=e.device)
-    dt = AIQMC_F32 if e.dtype == torch.float32 else AIQMC_F64
-    check(load().aiqmc_energy_stats(_ptr(e), dt, e.numel(), _ptr(out), 1 if finalize else 0, _stream(e.device)),
+    check(load().aiqmc_energy_stats(_ptr(e), _dt(e), e.numel(), _ptr(out), 1 if finalize else 0, _stream(e.device)),
           "aiqmc_energy_stats")
     return out
 
@@ -284,16 +295,11 @@ def loss_weights(e_l: torch.Tensor, clip_scale: float, center_at_clipped: bool, 
     cr = torch.empty_like(er)
     ci = torch.empty_like(er) if cplx else None
     st = torch.empty(5, dtype=torch.float64, device=er.device)
-    dt = AIQMC_F32 if er.dtype == torch.float32 else AIQMC_F64
-    check(load().aiqmc_loss_weights(_ptr(er), _ptr(ei), dt, n, float(clip_scale), 1 if center_at_clipped else 0,
+    check(load().aiqmc_loss_weights(_ptr(er), _ptr(ei), _dt(er), n, float(clip_scale), 1 if center_at_clipped else 0,
                                     float(wscale), _ptr(wr), _ptr(wi), _ptr(cr), _ptr(ci), _ptr(st),
                                     _stream(er.device)), "aiqmc_loss_weights")
     clipped = torch.complex(cr, ci) if cplx else cr
     return wr, wi, clipped.reshape(e_l.shape), st
-
-
-def _dt(t: torch.Tensor) -> int:
-    return AIQMC_F32 if t.dtype == torch.float32 else AIQMC_F64
 
 
 def loss_level(level: int, er: torch.Tensor, ei: Optional[torch.Tensor], L1=None, L2=None,
@@ -337,8 +343,7 @@ def loss_final(L1: torch.Tensor, L3: torch.Tensor, P: int, g0: bool, center_at_c
     grad = torch.empty(P, dtype=dtype, device=L1.device)
     stats = torch.empty(6, dtype=torch.float64, device=L1.device)
     check(load().aiqmc_loss_final(_ptr(L1), _ptr(L3), P, 1 if g0 else 0, 1 if center_at_clipped else 0, int(world),
-                                  AIQMC_F32 if dtype == torch.float32 else AIQMC_F64, _ptr(grad), _ptr(stats),
-                                  _stream(L1.device)), "aiqmc_loss_final")
+                                  _dt(dtype), _ptr(grad), _ptr(stats), _stream(L1.device)), "aiqmc_loss_final")
     return grad, stats
 
 
@@ -499,6 +504,7 @@ class Context:
         self.A = int(natoms)
         self.nspins = (int(nspins[0]), int(nspins[1]))
         self._keep = []
+        self._ecp_keep, self._ecp_token = None, None   # set_ecp: the uploaded tables and their identity
 
         def dbl(a):
             a = np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape(-1))
@@ -516,7 +522,7 @@ class Context:
         cfg.nelectrons = self.N
         cfg.natoms = self.A
         cfg.nspins[0], cfg.nspins[1] = int(nspins[0]), int(nspins[1])
-        cfg.dtype = AIQMC_F32 if dtype == torch.float32 else AIQMC_F64
+        cfg.dtype = _dt(dtype)
         cfg.device = int(device)
         cfg.atoms = dbl(atoms)
         cfg.charges = dbl(charges)
@@ -536,6 +542,15 @@ class Context:
         self._h = h
         self._lib = lib
         self.nparams = int(lib.aiqmc_param_count(h))
+
+    @classmethod
+    def for_system(cls, system, dtype: torch.dtype = torch.float32, device: int = 0, atoms=None) -> "Context":
+        """The context of a system description: anything with nelectrons, natoms, nspins, atoms,
+        charges and tables() (aiqmc.systems.System, oracle.system's).  atoms: another geometry."""
+        t = system.tables()
+        return cls(system.nelectrons, system.natoms, system.nspins, system.atoms if atoms is None else atoms,
+                   system.charges, t["spin_up_indices"], t["spin_down_indices"], t["parallel_indices"],
+                   t["antiparallel_indices"], dtype=dtype, device=device)
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -569,6 +584,21 @@ class Context:
         if pos.shape[-1] != 3 * self.N:
             raise ValueError(f"positions must have trailing dim 3N={3 * self.N}, got {tuple(pos.shape)}")
         return pos.reshape(-1, 3 * self.N)
+
+    def _inplace(self, pos: torch.Tensor, who: str, note: str = " (updated in place)") -> int:
+        """The walker count B of positions a sweep updates in place."""
+        if not (pos.is_cuda and pos.dtype == self.dtype and pos.is_contiguous()):
+            raise ValueError(f"{who} needs a contiguous device tensor of the context dtype{note}")
+        return pos.numel() // (3 * self.N)
+
+    def _rot(self, rot: Optional[torch.Tensor], B: int) -> Optional[torch.Tensor]:
+        """Injected grid rotations [B,3,3] in the context's dtype on its device (None: Philox)."""
+        if rot is None:
+            return None
+        r = rot.to(self.device, self.dtype).contiguous()
+        if r.numel() != 9 * B:
+            raise ValueError("rot must be [B,3,3]")
+        return r
 
     def set_params(self, flat: np.ndarray):
         flat = np.ascontiguousarray(np.asarray(flat, dtype=np.float64).reshape(-1))
@@ -658,11 +688,7 @@ class Context:
         p = self._pos(pos)
         B = p.shape[0]
         out = torch.empty(len(COMPONENT_NAMES), B, dtype=self.dtype, device=self.device)
-        r = None
-        if rot is not None:
-            r = rot.to(self.device, self.dtype).contiguous()
-            if r.numel() != 9 * B:
-                raise ValueError("rot must be [B,3,3]")
+        r = self._rot(rot, B)
         mode = AIQMC_RNG_HOST if r is not None else AIQMC_RNG_PHILOX
         with torch.cuda.device(self.device):
             check(self._lib.aiqmc_energy_components(self._h, _ptr(p), B, 1 if complex_output else 0, mode, _ptr(r),
@@ -858,10 +884,7 @@ class Context:
                                                          _stream(self.device)), "aiqmc_debug_local_energy_forward")
         return el, logabs, grad
 
-    def logpsi_param_grad(self, pos: torch.Tensor, weights: Optional[torch.Tensor] = None,
-                          want_logabs: bool = False):
-        """d log|psi| / d theta in canonical (tree_flatten) order: [B, P] per walker, or [P] =
-        sum_b weights[b] d log|psi_b| / d theta when weights [B] are given."""
+    def _param_grad(self, fn, what: str, pos: torch.Tensor, weights: Optional[torch.Tensor], want_value: bool):
         p = self._pos(pos)
         B = p.shape[0]
         w = None
@@ -872,10 +895,22 @@ class Context:
             out = torch.empty(self.nparams, dtype=self.dtype, device=self.device)
         else:
             out = torch.empty(B, self.nparams, dtype=self.dtype, device=self.device)
-        la = torch.empty(B, dtype=self.dtype, device=self.device) if want_logabs else None
-        check(self._lib.aiqmc_logpsi_param_grad(self._h, _ptr(p), B, _ptr(w), _ptr(out), _ptr(la),
-                                                _stream(self.device)), "aiqmc_logpsi_param_grad")
-        return (out, la) if want_logabs else out
+        val = torch.empty(B, dtype=self.dtype, device=self.device) if want_value else None
+        check(fn(self._h, _ptr(p), B, _ptr(w), _ptr(out), _ptr(val), _stream(self.device)), what)
+        return (out, val) if want_value else out
+
+    def logpsi_param_grad(self, pos: torch.Tensor, weights: Optional[torch.Tensor] = None,
+                          want_logabs: bool = False):
+        """d log|psi| / d theta in canonical (tree_flatten) order: [B, P] per walker, or [P] =
+        sum_b weights[b] d log|psi_b| / d theta when weights [B] are given."""
+        return self._param_grad(self._lib.aiqmc_logpsi_param_grad, "aiqmc_logpsi_param_grad", pos, weights,
+                                want_logabs)
+
+    def phase_param_grad(self, pos: torch.Tensor, weights: Optional[torch.Tensor] = None,
+                         want_phase: bool = False):
+        """d phase / d theta (phase = arg det A), same conventions as logpsi_param_grad."""
+        return self._param_grad(self._lib.aiqmc_phase_param_grad, "aiqmc_phase_param_grad", pos, weights,
+                                want_phase)
 
     def param_grad_weighted(self, pos: torch.Tensor, weights: torch.Tensor, phase: bool = False) -> torch.Tensor:
         """[K, P] = weights [K, B] times d f / d theta (f = log|psi|, or the phase), one gradient pass."""
@@ -889,31 +924,11 @@ class Context:
                                                   _ptr(out), None, _stream(self.device)), "aiqmc_param_grad_weighted")
         return out
 
-    def phase_param_grad(self, pos: torch.Tensor, weights: Optional[torch.Tensor] = None,
-                         want_phase: bool = False):
-        """d phase / d theta (phase = arg det A), same conventions as logpsi_param_grad."""
-        p = self._pos(pos)
-        B = p.shape[0]
-        w = None
-        if weights is not None:
-            w = weights.to(self.device, self.dtype).contiguous()
-            if w.numel() != B:
-                raise ValueError("weights must have one entry per walker")
-            out = torch.empty(self.nparams, dtype=self.dtype, device=self.device)
-        else:
-            out = torch.empty(B, self.nparams, dtype=self.dtype, device=self.device)
-        ph = torch.empty(B, dtype=self.dtype, device=self.device) if want_phase else None
-        check(self._lib.aiqmc_phase_param_grad(self._h, _ptr(p), B, _ptr(w), _ptr(out), _ptr(ph),
-                                               _stream(self.device)), "aiqmc_phase_param_grad")
-        return (out, ph) if want_phase else out
-
     # -- DMC (DMC/drift_diffusion.py, S_matrix.py, dmc.py, branch.py) -------------
     def dmc_drift_diffusion(self, pos: torch.Tensor, tstep: float, gauss1=None, gauss2=None, u=None, seed: int = 0,
                             offset: int = 0):
         """In-place drift-diffusion step; returns (grad_eff_old, grad_new_eff, tdamp[3] float64)."""
-        if not (pos.is_cuda and pos.dtype == self.dtype and pos.is_contiguous()):
-            raise ValueError("dmc_drift_diffusion needs a contiguous device tensor of the context dtype")
-        B = pos.numel() // (3 * self.N)
+        B = self._inplace(pos, "dmc_drift_diffusion", note="")
         if B * 3 * self.N != pos.numel():
             raise ValueError(f"positions must hold whole walkers of 3N={3 * self.N} coordinates")
         host = gauss1 is not None
@@ -1011,9 +1026,7 @@ class Context:
                    offset: int = 0):
         """In-place T-moves (DMC/Tmoves.py:32-225) on `pos`; returns the acceptance [B, N].
         rot [B,3,3], u_sel [B], u_acc [B,N]: injected draws (parity mode); all None: Philox."""
-        if not (pos.is_cuda and pos.dtype == self.dtype and pos.is_contiguous()):
-            raise ValueError("dmc_tmoves needs a contiguous device tensor of the context dtype (updated in place)")
-        B = pos.numel() // (3 * self.N)
+        B = self._inplace(pos, "dmc_tmoves")
         host = rot is not None
         if host != (u_sel is not None) or host != (u_acc is not None):
             raise ValueError("rot, u_sel and u_acc are injected together or not at all")
@@ -1032,27 +1045,60 @@ class Context:
             raise ValueError(f"expected {n} values, got {t.numel()}")
         return t
 
+    def _ecp_arrays(self, tables, list_l: int):
+        """The six tables as private read-only float64 arrays in the C-ABI's shapes ([A][KL],
+        [A][list_l+1][KN]), and their identity: list_l and the arrays' bytes."""
+        shapes = [(self.A, -1)] * 3 + [(self.A, int(list_l) + 1, -1)] * 3
+        arr = [np.array(a, dtype=np.float64, order="C").reshape(sh) for a, sh in zip(tables, shapes)]
+        if len({a.shape for a in arr[:3]}) != 1 or len({a.shape for a in arr[3:]}) != 1:
+            raise ValueError("ECP tables of one kind must share their shape")
+        for a in arr:
+            a.flags.writeable = False
+        return arr, (int(list_l),) + tuple(a.tobytes() for a in arr)
+
+    def _upload_ecp(self, arr, token) -> None:
+        e = AiqmcEcp()
+        e.list_l = token[0]
+        e.n_local = arr[0].shape[1]
+        e.n_nonlocal = arr[3].shape[2]
+        dp = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+        e.rn_local, e.local_coes, e.local_exps = (dp(a) for a in arr[:3])
+        e.rn_non_local, e.non_local_coes, e.non_local_exps = (dp(a) for a in arr[3:])
+        with torch.cuda.device(self.device):
+            rc = self._lib.aiqmc_set_ecp(self._h, ctypes.byref(e))
+        if rc == AIQMC_EHIP:   # the library dropped its tables; a refused argument leaves the old ones in place
+            self._ecp_keep, self._ecp_token = None, None
+        check(rc, "aiqmc_set_ecp")
+        self._ecp_keep, self._ecp_token = arr, token
+
     def set_ecp(self, rn_local, local_coes, local_exps, rn_non_local, non_local_coes, non_local_exps,
                 list_l: int):
         """Pseudopotential tables in the reference drivers' shapes (single_atom_C.py:13-23):
-        rn_local/local_coes/local_exps [A][KL], rn_non_local/... [A][list_l+1][KN]."""
-        A = self.A
-        loc = [np.ascontiguousarray(np.asarray(a, np.float64).reshape(A, -1)) for a in
-               (rn_local, local_coes, local_exps)]
-        nl = [np.ascontiguousarray(np.asarray(a, np.float64).reshape(A, int(list_l) + 1, -1)) for a in
-              (rn_non_local, non_local_coes, non_local_exps)]
-        if len({a.shape for a in loc}) != 1 or len({a.shape for a in nl}) != 1:
-            raise ValueError("ECP tables of one kind must share their shape")
-        self._ecp_keep = loc + nl
-        e = AiqmcEcp()
-        e.list_l = int(list_l)
-        e.n_local = loc[0].shape[1]
-        e.n_nonlocal = nl[0].shape[2]
-        dp = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
-        e.rn_local, e.local_coes, e.local_exps = (dp(a) for a in loc)
-        e.rn_non_local, e.non_local_coes, e.non_local_exps = (dp(a) for a in nl)
-        with torch.cuda.device(self.device):
-            check(self._lib.aiqmc_set_ecp(self._h, ctypes.byref(e)), "aiqmc_set_ecp")
+        rn_local/local_coes/local_exps [A][KL], rn_non_local/... [A][list_l+1][KN].  Uploads them
+        and records what this context now holds (ecp, ensure_ecp)."""
+        self._upload_ecp(*self._ecp_arrays((rn_local, local_coes, local_exps, rn_non_local, non_local_coes,
+                                            non_local_exps), list_l))
+
+    def set_ecp_tables(self, e):
+        """set_ecp from an object with the seven fields (aiqmc.systems.EcpTables, oracle.pphamiltonian's, EcpView)."""
+        self.set_ecp(*(getattr(e, k) for k in ECP_TABLE_NAMES), e.list_l)
+
+    def ensure_ecp(self, rn_local, local_coes, local_exps, rn_non_local, non_local_coes, non_local_exps,
+                   list_l: int) -> bool:
+        """set_ecp unless the context already holds exactly these tables; True when it uploaded.
+        The drop-in closures call it on every evaluation: only the context knows what it holds,
+        so a set_ecp from anywhere else in between is seen."""
+        arr, token = self._ecp_arrays((rn_local, local_coes, local_exps, rn_non_local, non_local_coes,
+                                       non_local_exps), list_l)
+        if token == self._ecp_token:
+            return False
+        self._upload_ecp(arr, token)
+        return True
+
+    @property
+    def ecp(self) -> Optional[EcpView]:
+        """The tables this context holds, by name (read-only arrays in the C-ABI's shapes), or None."""
+        return None if self._ecp_token is None else EcpView(*self._ecp_keep, self._ecp_token[0])
 
     def local_energy_ecp(self, pos: torch.Tensor, rot: Optional[torch.Tensor] = None, seed: int = 0,
                          offset: int = 0, want_quadrature: bool = False, complex_output: bool = False):
@@ -1063,11 +1109,7 @@ class Context:
         B = p.shape[0]
         er = torch.empty(B, dtype=self.dtype, device=self.device)
         ei = torch.empty(B, dtype=self.dtype, device=self.device)
-        r = None
-        if rot is not None:
-            r = rot.to(self.device, self.dtype).contiguous()
-            if r.numel() != 9 * B:
-                raise ValueError("rot must be [B,3,3]")
+        r = self._rot(rot, B)
         nq = B * self.N * self.A * ECP_NQ
         lq = torch.empty(nq, dtype=self.dtype, device=self.device) if want_quadrature else None
         pq = torch.empty(nq, dtype=self.dtype, device=self.device) if want_quadrature else None
@@ -1090,9 +1132,7 @@ class Context:
     def mc_step(self, pos: torch.Tensor, nsteps: int, tstep: float, gauss1=None, gauss2=None, u=None,
                 seed: int = 0, offset: int = 0, count_accepts: bool = False):
         """In-place Metropolis on `pos` (must be a contiguous device tensor of ctx dtype)."""
-        if not (pos.is_cuda and pos.dtype == self.dtype and pos.is_contiguous()):
-            raise ValueError("mc_step needs a contiguous device tensor of the context dtype (updated in place)")
-        B = pos.numel() // (3 * self.N)
+        B = self._inplace(pos, "mc_step")
         host = gauss1 is not None
         acc = torch.zeros(B, dtype=torch.int32, device=self.device) if count_accepts else None
         if host:

@@ -36,6 +36,8 @@ import torch
 import torch.distributed as dist
 
 from .. import _lib, constants
+from ..utils.utils import np64
+from ..wavefunction_Ynlm.nn import as_positions, network_of
 from . import corrsamples, jacobianWeights
 
 
@@ -50,12 +52,8 @@ class EnergyDifferences:
     ess: torch.Tensor
 
 
-def _np64(x) -> np.ndarray:
-    return np.asarray(x.detach().cpu() if isinstance(x, torch.Tensor) else x, dtype=np.float64)
-
-
 def _primary_atoms(atoms) -> np.ndarray:
-    a = _np64(atoms)
+    a = np64(atoms)
     return a.reshape(-1, a.shape[-2], a.shape[-1])[0] if a.ndim == 3 else a
 
 
@@ -99,12 +97,6 @@ def _autograd_local_energy(network, params, pos, spins, atoms, charges):
     return v - 0.5 * (lap + (g * g).sum(-1))
 
 
-def _ecp_tables(ecp):
-    names = ("rn_local", "local_coes", "local_exps", "rn_non_local", "non_local_coes", "non_local_exps")
-    tables = tuple(_np64(getattr(ecp, k)) for k in names)
-    return tables, int(ecp.list_l)
-
-
 def energy_differences(network, params, data, new_atoms, *, ecp=None, seed=0, offset=0) -> EnergyDifferences:
     """E(R'_m) - E(R) for the geometries new_atoms [M, A, 3] on the walkers data.positions [B, 3N]
     sampled at data.atoms (see the module docstring).  The local energy is the all-electron one;
@@ -114,10 +106,9 @@ def energy_differences(network, params, data, new_atoms, *, ecp=None, seed=0, of
     well.  ``seed`` may instead be an ``Energy.pphamiltonian.HostRotations`` (injected rotations,
     the parity mode of the pp local energy)."""
     f = getattr(network, "apply", network)
-    net = getattr(f, "_aiqmc_network", None)
-    pos = data.positions if isinstance(data.positions, torch.Tensor) else torch.as_tensor(np.asarray(data.positions))
+    net = network_of(f, None)
     atoms = _primary_atoms(data.atoms)
-    na = _np64(new_atoms)
+    na = np64(new_atoms)
     if na.ndim == 2:
         na = na[None]
     if na.ndim != 3 or na.shape[1:] != atoms.shape:
@@ -129,9 +120,10 @@ def energy_differences(network, params, data, new_atoms, *, ecp=None, seed=0, of
     if net is None:
         if ecp is not None:
             raise NotImplementedError("energy_differences: the ccECP local energy needs an aiqmc network")
+        pos = as_positions(data.positions)
         p = pos.reshape(-1, pos.shape[-1]).to(torch.float64)
         at, nat = torch.as_tensor(atoms).to(p.device), torch.as_tensor(na).to(p.device)
-        ch = torch.as_tensor(_np64(data.charges)).reshape(-1)[:atoms.shape[0]].to(p.device)
+        ch = torch.as_tensor(np64(data.charges)).reshape(-1)[:atoms.shape[0]].to(p.device)
         el = getattr(f, "local_energy", None)
         e_l = (lambda x, a: torch.as_tensor(el(params, x, a, ch))) if el is not None else (
             lambda x, a: _autograd_local_energy(f, params, x, data.spins, a, ch))
@@ -143,8 +135,8 @@ def energy_differences(network, params, data, new_atoms, *, ecp=None, seed=0, of
         real = lambda t: (t.real if torch.is_complex(t) else t).to(torch.float64)
         return reduce_levels(real(la(p, at)), real(e_l(p, at)), real(la1), logjac, real(e1))
 
-    dtype = pos.dtype if pos.dtype in (torch.float32, torch.float64) else torch.float32
-    ctx0 = net.bind(params, atoms, dtype)
+    ctx0, pos = net.bind_positions(params, data.positions, atoms)
+    dtype = ctx0.dtype
     ctxs = [net.bind(params, na[m], dtype) for m in range(M)]
     p = ctx0._pos(pos)
     B = p.shape[0]
@@ -158,15 +150,12 @@ def energy_differences(network, params, data, new_atoms, *, ecp=None, seed=0, of
             la1[m].copy_(la_m)
     else:
         from ..Energy.pphamiltonian import HostRotations
-        tables, list_l = _ecp_tables(ecp)
-        token = (list_l,) + tuple(t.tobytes() for t in tables)
+        tables = tuple(np64(getattr(ecp, k)) for k in _lib.ECP_TABLE_NAMES)
         kw = dict(rot=torch.as_tensor(seed.rot)) if isinstance(seed, HostRotations) else dict(
             seed=int(getattr(seed, "seed", seed)), offset=int(getattr(seed, "offset", offset)))
 
         def pp(c, x):
-            if getattr(c, "_ecp_token", None) != token:
-                c.set_ecp(*tables, list_l=list_l)
-                c._ecp_token = token
+            c.ensure_ecp(*tables, list_l=int(ecp.list_l))
             return c.local_energy_ecp(x, **kw).real, c.logpsi(x, with_phase=False)[0]
 
         e0, la0 = pp(ctx0, p)

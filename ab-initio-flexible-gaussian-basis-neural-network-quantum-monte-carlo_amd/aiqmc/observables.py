@@ -40,15 +40,7 @@ import numpy as np
 import torch
 
 from . import constants
-
-
-def _positions(data) -> torch.Tensor:
-    pos = data.positions
-    return pos if isinstance(pos, torch.Tensor) else torch.as_tensor(np.asarray(pos))
-
-
-def _kernel_dtype(pos: torch.Tensor):
-    return pos.dtype if pos.dtype in (torch.float32, torch.float64) else torch.float32
+from .wavefunction_Ynlm.nn import as_positions, kernel_dtype, network_of
 
 
 def _spin_slots(spins, nspins: Tuple[int, int], nelectrons: int):
@@ -96,21 +88,19 @@ def make_s2(signed_network, nspins: Sequence[int], assign_spin: bool = True, sta
         raise NotImplementedError("make_s2: states != 0 (the excited-state machinery) is not built")
     nspins = (int(nspins[0]), int(nspins[1]))
     diag = _s2_diagonal(nspins)
-    net = getattr(signed_network, "_aiqmc_network", None)
+    net = network_of(signed_network, None)
 
     if net is not None:
         if tuple(net.nspins) != nspins:
             raise ValueError(f"make_s2: nspins={nspins} differ from the network's {tuple(net.nspins)}")
 
         def _pairs(params, data):
-            pos = _positions(data)
-            ctx = net.bind(params, data.atoms, _kernel_dtype(pos))
+            ctx, pos = net.bind_positions(params, data.positions, data.atoms)
             return pos, ctx.spin_squared(pos, want_pairs=True)
 
         def s2_estimator(params, data, state=None):
             del state
-            pos = _positions(data)
-            ctx = net.bind(params, data.atoms, _kernel_dtype(pos))
+            ctx, pos = net.bind_positions(params, data.positions, data.atoms)
             return ctx.spin_squared(pos).reshape(pos.shape[:-1])
 
         def pair_ratios(params, data):
@@ -119,7 +109,7 @@ def make_s2(signed_network, nspins: Sequence[int], assign_spin: bool = True, sta
             return r.reshape(*pos.shape[:-1], *nspins)
     else:
         def pair_ratios(params, data):
-            pos = _positions(data)
+            pos = as_positions(data.positions)
             n3 = pos.shape[-1]
             flat = pos.reshape(-1, n3)
             up, dn = _spin_slots(data.spins, nspins, n3 // 3)
@@ -150,13 +140,13 @@ def make_dipole(signed_network, states: int = 0):
     """See the module docstring."""
     if states:
         raise NotImplementedError("make_dipole: states != 0 (the excited-state machinery) is not built")
-    net = getattr(signed_network, "_aiqmc_network", None)
+    net = network_of(signed_network, None)
 
     def dipole_estimator(params, data, state=None):
         del params, state
-        pos = _positions(data)
+        pos = as_positions(data.positions)
         if net is not None:
-            ctx = net.context(data.atoms, _kernel_dtype(pos))
+            ctx = net.context(data.atoms, kernel_dtype(pos))
             return ctx.dipole(pos).reshape(*pos.shape[:-1], 3)
         atoms = torch.as_tensor(np.asarray(data.atoms), dtype=pos.dtype, device=pos.device).reshape(-1, 3)
         charges = torch.as_tensor(np.asarray(data.charges), dtype=pos.dtype, device=pos.device).reshape(-1)
@@ -231,7 +221,7 @@ class DensityAccumulator:
 
     def __init__(self, signed_network, nspins, grid, radial, pair):
         self.nspins = (int(nspins[0]), int(nspins[1]))
-        self._net = getattr(signed_network, "_aiqmc_network", None)
+        self._net = network_of(signed_network, None)
         if self._net is not None and tuple(self._net.nspins) != self.nspins:
             raise ValueError(f"make_density: nspins={self.nspins} differ from the network's {tuple(self._net.nspins)}")
         self.cfg = _density_cfg_checked(grid, radial, pair)
@@ -302,12 +292,12 @@ class DensityAccumulator:
         """Bins every walker of ``data.positions [..., 3N]`` (weights: one per walker, or None for
         unit weights).  No host synchronisation on the kernel path."""
         del params   # the density needs the walkers only
-        pos = _positions(data)
+        pos = as_positions(data.positions)
         n3 = pos.shape[-1]
         if n3 != 3 * sum(self.nspins):
             raise ValueError(f"positions have {n3 // 3} electrons, nspins={self.nspins}")
         if self._net is not None:
-            ctx = self._net.context(data.atoms, _kernel_dtype(pos))
+            ctx = self._net.context(data.atoms, kernel_dtype(pos))
             self._ensure(ctx.A, ctx.device)
             ctx.density_accumulate(pos, self.words, self.cfg, weights)
             return

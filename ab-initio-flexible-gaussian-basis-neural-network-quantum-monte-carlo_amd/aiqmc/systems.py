@@ -56,10 +56,7 @@ class System:
         """A HIP context (libaiqmc_hip.so) for this system."""
         import torch
         from . import _lib
-        t = self.tables()
-        return _lib.Context(self.nelectrons, self.natoms, self.nspins, self.atoms, self.charges,
-                            t["spin_up_indices"], t["spin_down_indices"], t["parallel_indices"],
-                            t["antiparallel_indices"], dtype=dtype or torch.float32, device=device)
+        return _lib.Context.for_system(self, dtype or torch.float32, device)
 
     def make_network(self):
         """nn.make_ai_net with this system's closure tables (the drivers' call, e.g.

@@ -143,6 +143,29 @@ def _first(x):
     return np.asarray(x, dtype=np.int32).reshape(-1)
 
 
+def as_positions(positions) -> torch.Tensor:
+    """Walker positions as a tensor: a tensor is passed through as it is, anything else goes
+    through NumPy and keeps NumPy's dtype (a list of Python floats gives float64)."""
+    return positions if isinstance(positions, torch.Tensor) else torch.as_tensor(np.asarray(positions))
+
+
+def kernel_dtype(pos: torch.Tensor) -> torch.dtype:
+    """The dtype of the context that serves `pos`: its own when a kernel is built for it, else float32."""
+    return pos.dtype if pos.dtype in (torch.float32, torch.float64) else torch.float32
+
+
+def network_of(f, who: Optional[str]):
+    """The AINet behind `f`: make_ai_net tags its apply with it, and make_log_network, select_output
+    and every drop-in factory hand the tag on to the closure they return.  An untagged `f` raises a
+    TypeError naming `who`; who=None returns None instead (callers with a generic path of their own)."""
+    net = getattr(f, "_aiqmc_network", None)
+    if net is None and who is not None:
+        raise TypeError(f"{who}: expected the apply of an aiqmc make_ai_net Network or a closure built from it "
+                        "(nn.make_log_network, aiqmc.Energy, aiqmc.Loss); the HIP kernels are specific to that "
+                        "ansatz and there is no fallback")
+    return net
+
+
 def _atoms_charges(atoms, charges):
     a = atoms.detach().cpu().numpy() if isinstance(atoms, torch.Tensor) else np.asarray(atoms)
     c = charges.detach().cpu().numpy() if isinstance(charges, torch.Tensor) else np.asarray(charges)
@@ -260,12 +283,16 @@ class AINet:
         self._loaded[k] = (_leaf_key(leaves), digest)
         return ctx
 
+    def bind_positions(self, params, positions, atoms, device: Optional[int] = None, force: bool = False):
+        """(ctx, pos), the prologue of every drop-in closure: pos = as_positions(positions) and the
+        context of kernel_dtype(pos) with `params` uploaded (bind)."""
+        pos = as_positions(positions)
+        return self.bind(params, atoms, kernel_dtype(pos), device, force), pos
+
     # -- apply (nn.py:545-551) --------------------------------------------------
     def apply(self, params, pos, spins=None, atoms=None, charges=None):
         del spins, charges   # closures, as in the reference
-        pos_t = pos if isinstance(pos, torch.Tensor) else torch.as_tensor(np.asarray(pos))
-        dtype = pos_t.dtype if pos_t.dtype in (torch.float32, torch.float64) else torch.float32
-        ctx = self.bind(params, atoms, dtype)
+        ctx, pos_t = self.bind_positions(params, pos, atoms)
         logabs, phase = ctx.logpsi(pos_t)
         shape = pos_t.shape[:-1]
         return phase.reshape(shape), logabs.reshape(shape)
@@ -275,9 +302,7 @@ class AINet:
         Phi * Yt * exp(J_ee/N) exp(J_ae/N) whose slogdet apply() returns (a one-element list, as
         the reference's ``total_orbitals_jastrow``; ``determinants`` is ignored, Q10)."""
         del spins, charges
-        pos_t = pos if isinstance(pos, torch.Tensor) else torch.as_tensor(np.asarray(pos))
-        dtype = pos_t.dtype if pos_t.dtype in (torch.float32, torch.float64) else torch.float32
-        ctx = self.bind(params, atoms, dtype)
+        ctx, pos_t = self.bind_positions(params, pos, atoms)
         m = ctx.orbitals(pos_t)
         return [m.reshape(*pos_t.shape[:-1], self.nelectrons, self.nelectrons)]
 
@@ -312,9 +337,7 @@ def make_log_network(signed_network):
     (``log_network`` in DMC/main_dmc.py:91-93, main_pp_adam_muti_GPU.py:119-121):
     log|psi| + i phase, tagged with the aiqmc network so that the pp / T-move drop-ins
     can dispatch to the kernels."""
-    net = getattr(signed_network, "_aiqmc_network", None)
-    if net is None:
-        raise TypeError("make_log_network: signed_network must be an aiqmc make_ai_net apply")
+    net = network_of(signed_network, "make_log_network")
 
     def log_network(*args, **kwargs):
         phase, mag = signed_network(*args, **kwargs)

@@ -69,9 +69,7 @@ def _ctx(name, dtype=torch.float64):
     from oracle import system
     from aiqmc import _lib
     s = system.make_system(name)
-    t = s.tables()
-    ctx = _lib.Context(s.nelectrons, s.natoms, s.nspins, s.atoms, s.charges, t["spin_up_indices"],
-                       t["spin_down_indices"], t["parallel_indices"], t["antiparallel_indices"], dtype=dtype, device=0)
+    ctx = _lib.Context.for_system(s, dtype)
     return s, ctx
 
 
@@ -244,11 +242,8 @@ def _tm_ctx(dtype, ecp, sysname="C_ecp"):
     from oracle import system
     from aiqmc import _lib
     s = system.make_system(sysname)
-    t = s.tables()
-    ctx = _lib.Context(s.nelectrons, s.natoms, s.nspins, s.atoms, s.charges, t["spin_up_indices"],
-                       t["spin_down_indices"], t["parallel_indices"], t["antiparallel_indices"], dtype=dtype, device=0)
-    ctx.set_ecp(ecp.rn_local, ecp.local_coes, ecp.local_exps, ecp.rn_non_local, ecp.non_local_coes,
-                ecp.non_local_exps, ecp.list_l)
+    ctx = _lib.Context.for_system(s, dtype)
+    ctx.set_ecp_tables(ecp)
     return s, ctx
 
 

@@ -120,11 +120,9 @@ def _ecp_ctx(dtype, name="C_ecp"):
     from oracle import system
     from aiqmc import _lib
     s = system.make_system(name)
-    t = s.tables()
-    ctx = _lib.Context(s.nelectrons, s.natoms, s.nspins, s.atoms, s.charges, t["spin_up_indices"],
-                       t["spin_down_indices"], t["parallel_indices"], t["antiparallel_indices"], dtype=dtype, device=0)
+    ctx = _lib.Context.for_system(s, dtype)
     e = {"C_ecp": pp.c_atom_ccecp, "C2_ecp": pp.c2_ccecp, "CO2_ecp": pp.co2_ccecp}[name]()
-    ctx.set_ecp(e.rn_local, e.local_coes, e.local_exps, e.rn_non_local, e.non_local_coes, e.non_local_exps, e.list_l)
+    ctx.set_ecp_tables(e)
     return s, ctx
 
 
@@ -186,12 +184,8 @@ def test_ecp_packed_three_atoms_match_oracle(name):
     pos = system.init_electrons(rng, s.atoms, s.charges, 2, 1.0)
     rots = pp.haar_rotations(rng, 2)
     ref, _, _, _ = pp.batch_local_energy_pp(network.Network(s), network.to_torch(params), ecp, torch.tensor(pos), rots)
-    t = s.tables()
-    ctx = _lib.Context(s.nelectrons, s.natoms, s.nspins, s.atoms, s.charges, t["spin_up_indices"],
-                       t["spin_down_indices"], t["parallel_indices"], t["antiparallel_indices"], dtype=torch.float64,
-                       device=0)
-    ctx.set_ecp(ecp.rn_local, ecp.local_coes, ecp.local_exps, ecp.rn_non_local, ecp.non_local_coes,
-                ecp.non_local_exps, ecp.list_l)
+    ctx = _lib.Context.for_system(s, torch.float64)
+    ctx.set_ecp_tables(ecp)
     ctx.set_params(system.flatten_params(params))
     e = ctx.local_energy_ecp(torch.tensor(pos, device="cuda"), rot=torch.tensor(rots, device="cuda"))
     torch.cuda.synchronize()
@@ -242,10 +236,7 @@ def test_ecp_errors():
     from oracle import system
     from aiqmc import _lib
     s = system.make_system("C_ecp")
-    t = s.tables()
-    ctx = _lib.Context(s.nelectrons, s.natoms, s.nspins, s.atoms, s.charges, t["spin_up_indices"],
-                       t["spin_down_indices"], t["parallel_indices"], t["antiparallel_indices"],
-                       dtype=torch.float64, device=0)
+    ctx = _lib.Context.for_system(s, torch.float64)
     ctx.set_params(system.flatten_params(system.init_params(np.random.default_rng(0), s)))
     pos = torch.zeros(2, 12, dtype=torch.float64, device="cuda")
     with pytest.raises(RuntimeError, match="aiqmc_set_ecp has not been called"):

@@ -80,10 +80,7 @@ def _case(shape):
 def _ctx(s, params, dtype):
     from oracle import system
     from aiqmc import _lib
-    t = s.tables()
-    ctx = _lib.Context(s.nelectrons, s.natoms, s.nspins, s.atoms, s.charges, t["spin_up_indices"],
-                       t["spin_down_indices"], t["parallel_indices"], t["antiparallel_indices"], dtype=dtype,
-                       device=0)
+    ctx = _lib.Context.for_system(s, dtype)
     ctx.set_params(system.flatten_params(params))
     return ctx
 

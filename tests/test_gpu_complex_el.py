@@ -14,13 +14,10 @@ def _ctx_and_oracle(name, dtype, B, seed):
     from oracle import network, system
     from aiqmc import _lib
     s = system.make_system(name)
-    t = s.tables()
     rng = np.random.default_rng(seed)
     params = system.init_params(rng, s, randomize_aux=True)
     pos = system.init_electrons(rng, s.atoms, s.charges, B, 1.0)
-    ctx = _lib.Context(s.nelectrons, s.natoms, s.nspins, s.atoms, s.charges, t["spin_up_indices"],
-                       t["spin_down_indices"], t["parallel_indices"], t["antiparallel_indices"], dtype=dtype,
-                       device=0)
+    ctx = _lib.Context.for_system(s, dtype)
     ctx.set_params(system.flatten_params(params))
     return s, ctx, network.Network(s), params, pos
 
@@ -161,7 +158,7 @@ def test_pp_complex_output_one_call_matches_composition(dtype):
     ctx = s.context(dtype=dtype)
     ctx.set_params(flatten_params(s.make_network().init(3)))
     e = systems.ccecp_tables("C_ecp")
-    ctx.set_ecp(e.rn_local, e.local_coes, e.local_exps, e.rn_non_local, e.non_local_coes, e.non_local_exps, e.list_l)
+    ctx.set_ecp_tables(e)
     pos = init_electrons(5, None, s.atoms, s.charges, s.spins, 512, 1.0)[0].to("cuda", dtype).contiguous()
     one = ctx.local_energy_ecp(pos, seed=4, offset=2, complex_output=True)
     pp = ctx.local_energy_ecp(pos, seed=4, offset=2)

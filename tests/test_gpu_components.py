@@ -98,12 +98,9 @@ def _ctx(c, dtype, set_params=True):
     s, e = c["s"], c["ecp"]
     if (s.nelectrons, s.natoms) not in _lib.supported_shapes():
         pytest.skip(f"({s.nelectrons}, {s.natoms}) not in this library's shape list")
-    t = s.tables()
-    ctx = _lib.Context(s.nelectrons, s.natoms, s.nspins, s.atoms, s.charges, t["spin_up_indices"],
-                       t["spin_down_indices"], t["parallel_indices"], t["antiparallel_indices"], dtype=dtype,
-                       device=0)
+    ctx = _lib.Context.for_system(s, dtype)
     if e is not None:
-        ctx.set_ecp(e.rn_local, e.local_coes, e.local_exps, e.rn_non_local, e.non_local_coes, e.non_local_exps, e.list_l)
+        ctx.set_ecp_tables(e)
     if set_params:
         ctx.set_params(c["params"])
     return ctx

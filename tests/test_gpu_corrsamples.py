@@ -68,10 +68,7 @@ def _ctx(s, dtype, params=None, atoms=None):
     from aiqmc import _lib
     if (s.nelectrons, s.natoms) not in _lib.supported_shapes():
         pytest.skip(f"({s.nelectrons}, {s.natoms}) not in this library's shape list")
-    t = s.tables()
-    ctx = _lib.Context(s.nelectrons, s.natoms, s.nspins, s.atoms if atoms is None else atoms, s.charges,
-                       t["spin_up_indices"], t["spin_down_indices"], t["parallel_indices"],
-                       t["antiparallel_indices"], dtype=dtype, device=0)
+    ctx = _lib.Context.for_system(s, dtype, atoms=atoms)
     if params is not None:
         ctx.set_params(system.flatten_params(params))
     return ctx

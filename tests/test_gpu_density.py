@@ -31,10 +31,7 @@ def _ctx(name, dtype):
         atoms, per, spins = H.geometry(name)
         s = system.make_system(name)
         assert np.array_equal(s.atoms, atoms) and np.array_equal(s.spins, spins)
-        t = s.tables()
-        _CTX[(name, dtype)] = _lib.Context(s.nelectrons, s.natoms, s.nspins, atoms, s.charges, t["spin_up_indices"],
-                                           t["spin_down_indices"], t["parallel_indices"], t["antiparallel_indices"],
-                                           dtype=dtype, device=0)
+        _CTX[(name, dtype)] = _lib.Context.for_system(s, dtype, atoms=atoms)
     return _CTX[(name, dtype)]
 
 

@@ -12,15 +12,12 @@ from oracle import pphamiltonian as opp, system
 def _ctx(name, dtype=torch.float64, params=True, ecp=False):
     from aiqmc import _lib
     s = system.make_system(name)
-    t = s.tables()
-    ctx = _lib.Context(s.nelectrons, s.natoms, s.nspins, s.atoms, s.charges, t["spin_up_indices"],
-                       t["spin_down_indices"], t["parallel_indices"], t["antiparallel_indices"], dtype=dtype, device=0)
+    ctx = _lib.Context.for_system(s, dtype)
     if params:
         ctx.set_params(system.flatten_params(system.init_params(np.random.default_rng(3), s, randomize_aux=True)))
     if ecp:
         e = opp.c_atom_ccecp()
-        ctx.set_ecp(e.rn_local, e.local_coes, e.local_exps, e.rn_non_local, e.non_local_coes, e.non_local_exps,
-                    e.list_l)
+        ctx.set_ecp_tables(e)
     return s, ctx
 
 
@@ -66,7 +63,7 @@ def test_bad_arguments_raise():
     with pytest.raises(RuntimeError, match="aiqmc_set_ecp has not been called"):
         ctx.dmc_tmoves(pos.contiguous(), 0.1, seed=1)
     e = opp.c_atom_ccecp()
-    ctx.set_ecp(e.rn_local, e.local_coes, e.local_exps, e.rn_non_local, e.non_local_coes, e.non_local_exps, e.list_l)
+    ctx.set_ecp_tables(e)
     with pytest.raises(RuntimeError, match="tstep"):
         ctx.dmc_tmoves(pos.contiguous(), 0.0, seed=1)
     with pytest.raises(ValueError):

@@ -30,10 +30,7 @@ def _ctx(name, dtype, gaussian_only):
     from oracle import system
     from aiqmc import _lib
     s = system.make_system(name)
-    t = s.tables()
-    ctx = _lib.Context(s.nelectrons, s.natoms, s.nspins, s.atoms, s.charges, t["spin_up_indices"],
-                       t["spin_down_indices"], t["parallel_indices"], t["antiparallel_indices"], dtype=dtype,
-                       device=0)
+    ctx = _lib.Context.for_system(s, dtype)
     p = system.init_params(np.random.default_rng(1), s)
     if gaussian_only:
         for env in p["envelope"]:

@@ -28,10 +28,7 @@ def _ctx(name, dtype):
     from oracle import system
     from aiqmc import _lib
     s = system.make_system(name)
-    t = s.tables()
-    ctx = _lib.Context(s.nelectrons, s.natoms, s.nspins, s.atoms, s.charges, t["spin_up_indices"],
-                       t["spin_down_indices"], t["parallel_indices"], t["antiparallel_indices"], dtype=dtype,
-                       device=0)
+    ctx = _lib.Context.for_system(s, dtype)
     p = system.init_params(np.random.default_rng(1), s)
     # sigma = 0 drops the envelope's signed exp(-pi * ae) term (envelope.py:26-30), which grows
     # without bound along negative ae: with it |psi|^2 is not normalisable and the chains drift
@@ -142,10 +139,7 @@ def test_fp32_chain_on_the_init_parameters_early_iterations():
     res = {}
     for dtype in (torch.float64, torch.float32):
         s = system.make_system(name)
-        t = s.tables()
-        ctx = _lib.Context(s.nelectrons, s.natoms, s.nspins, s.atoms, s.charges, t["spin_up_indices"],
-                           t["spin_down_indices"], t["parallel_indices"], t["antiparallel_indices"], dtype=dtype,
-                           device=0)
+        ctx = _lib.Context.for_system(s, dtype)
         ctx.set_params(system.flatten_params(system.init_params(np.random.default_rng(1), s)))
         x = system.init_electrons(np.random.default_rng(0), s.atoms, s.charges, B, 1.0)
         pos = torch.tensor(x, dtype=dtype, device="cuda").contiguous()

@@ -20,10 +20,7 @@ def _ctx(name, dtype, params_seed=5):
     from oracle import system
     from aiqmc import _lib
     s = system.make_system(name)
-    t = s.tables()
-    ctx = _lib.Context(s.nelectrons, s.natoms, s.nspins, s.atoms, s.charges, t["spin_up_indices"],
-                       t["spin_down_indices"], t["parallel_indices"], t["antiparallel_indices"], dtype=dtype,
-                       device=0)
+    ctx = _lib.Context.for_system(s, dtype)
     p = system.init_params(np.random.default_rng(params_seed), s, randomize_aux=True)
     ctx.set_params(system.flatten_params(p))
     return s, ctx

@@ -28,10 +28,7 @@ def _ctx(dtype=torch.float32, flat=None):
     from oracle import system
     from aiqmc import _lib
     s = system.make_system("N2")
-    t = s.tables()
-    ctx = _lib.Context(s.nelectrons, s.natoms, s.nspins, s.atoms, s.charges, t["spin_up_indices"],
-                       t["spin_down_indices"], t["parallel_indices"], t["antiparallel_indices"], dtype=dtype,
-                       device=0)
+    ctx = _lib.Context.for_system(s, dtype)
     if flat is None:
         flat = system.flatten_params(system.init_params(np.random.default_rng(5), s, randomize_aux=True))
     ctx.set_params(flat)

@@ -80,10 +80,7 @@ def _ctx(s, params, dtype):
     from aiqmc import _lib
     if (s.nelectrons, s.natoms) not in _lib.supported_shapes():
         pytest.skip(f"({s.nelectrons}, {s.natoms}) not in this library's shape list")
-    t = s.tables()
-    ctx = _lib.Context(s.nelectrons, s.natoms, s.nspins, s.atoms, s.charges, t["spin_up_indices"],
-                       t["spin_down_indices"], t["parallel_indices"], t["antiparallel_indices"], dtype=dtype,
-                       device=0)
+    ctx = _lib.Context.for_system(s, dtype)
     ctx.set_params(system.flatten_params(params))
     return ctx
 
@@ -171,10 +168,7 @@ def test_two_calls_give_identical_bits(name):
 def test_empty_batch_and_missing_params():
     s, params, pos, _, _, _, _ = _case("H2")
     from aiqmc import _lib
-    t = s.tables()
-    ctx = _lib.Context(s.nelectrons, s.natoms, s.nspins, s.atoms, s.charges, t["spin_up_indices"],
-                       t["spin_down_indices"], t["parallel_indices"], t["antiparallel_indices"],
-                       dtype=torch.float64, device=0)
+    ctx = _lib.Context.for_system(s, torch.float64)
     x = torch.tensor(pos, device="cuda")
     with pytest.raises(RuntimeError, match="set_params"):
         ctx.spin_squared(x)

@@ -23,10 +23,7 @@ def _ctx(name, dtype):
     from oracle import system
     from aiqmc import _lib
     s = system.make_system(name)
-    t = s.tables()
-    return s, _lib.Context(s.nelectrons, s.natoms, s.nspins, s.atoms, s.charges, t["spin_up_indices"],
-                           t["spin_down_indices"], t["parallel_indices"], t["antiparallel_indices"],
-                           dtype=dtype, device=0)
+    return s, _lib.Context.for_system(s, dtype)
 
 
 def _golden(golden_dir, name):

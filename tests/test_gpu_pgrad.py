@@ -13,9 +13,7 @@ def _setup(name, dtype, B=4, seed=41):
     from oracle import system
     from aiqmc import _lib
     s = system.make_system(name)
-    t = s.tables()
-    ctx = _lib.Context(s.nelectrons, s.natoms, s.nspins, s.atoms, s.charges, t["spin_up_indices"],
-                       t["spin_down_indices"], t["parallel_indices"], t["antiparallel_indices"], dtype=dtype, device=0)
+    ctx = _lib.Context.for_system(s, dtype)
     rng = np.random.default_rng(seed)
     params = system.init_params(rng, s, randomize_aux=True)
     ctx.set_params(system.flatten_params(params))

@@ -71,14 +71,11 @@ def _walkers(name, B, seed=2, width=1.0):
 def _ctx(name, dtype, packed=True, ecp=False):
     from aiqmc import _lib
     s, flat = _setup(name)
-    t = s.tables()
-    ctx = _lib.Context(s.nelectrons, s.natoms, s.nspins, s.atoms, s.charges, t["spin_up_indices"],
-                       t["spin_down_indices"], t["parallel_indices"], t["antiparallel_indices"], dtype=dtype, device=0)
+    ctx = _lib.Context.for_system(s, dtype)
     if ecp:
         from oracle import pphamiltonian as pp
         e = pp.c_atom_ccecp()
-        ctx.set_ecp(e.rn_local, e.local_coes, e.local_exps, e.rn_non_local, e.non_local_coes, e.non_local_exps,
-                    e.list_l)
+        ctx.set_ecp_tables(e)
     ctx.set_params(flat)
     if not packed:
         ctx.set_packed_walkers(False)

@@ -38,9 +38,7 @@ def _be_ctx(dtype):
     from oracle import system
     from aiqmc import _lib
     s = system.make_system("Be")
-    t = s.tables()
-    ctx = _lib.Context(s.nelectrons, s.natoms, s.nspins, s.atoms, s.charges, t["spin_up_indices"],
-                       t["spin_down_indices"], t["parallel_indices"], t["antiparallel_indices"], dtype=dtype, device=0)
+    ctx = _lib.Context.for_system(s, dtype)
     return s, ctx
 
 

@@ -18,14 +18,11 @@ BATCHES = (3, 70, 5, 130)   # grow, reuse, regrow; 70 and 130 cross a wave / chu
 def _ctx(name, dtype):
     from aiqmc import _lib
     s = system.make_system(name)
-    t = s.tables()
-    ctx = _lib.Context(s.nelectrons, s.natoms, s.nspins, s.atoms, s.charges, t["spin_up_indices"],
-                       t["spin_down_indices"], t["parallel_indices"], t["antiparallel_indices"], dtype=dtype, device=0)
+    ctx = _lib.Context.for_system(s, dtype)
     ctx.set_params(system.flatten_params(system.init_params(np.random.default_rng(3), s, randomize_aux=True)))
     if name.endswith("_ecp"):
         e = opp.c_atom_ccecp()
-        ctx.set_ecp(e.rn_local, e.local_coes, e.local_exps, e.rn_non_local, e.non_local_coes, e.non_local_exps,
-                    e.list_l)
+        ctx.set_ecp_tables(e)
     return s, ctx
 
 

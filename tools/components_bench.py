@@ -61,7 +61,7 @@ def step(name, launches):
     ecp = sysname.endswith("_ecp")
     if ecp:
         t = systems.ccecp_tables(sysname)
-        ctx.set_ecp(t.rn_local, t.local_coes, t.local_exps, t.rn_non_local, t.non_local_coes, t.non_local_exps, t.list_l)
+        ctx.set_ecp_tables(t)
     N = s.nelectrons
     block = np.concatenate([np.tile(s.atoms[i], int(s.charges[i])) for i in range(s.natoms)])
     pos = torch.tensor(block[None] + np.random.default_rng(11).standard_normal((walkers, 3 * N)), dtype=torch.float32,

@@ -17,7 +17,7 @@ for name in os.environ.get("ECP_SYSTEMS", "C_ecp C2_ecp CO2_ecp").split():
         ctx = s.context(dtype=dt)
         ctx.set_params(flatten_params(s.make_network().init(1)))
         e = systems.ccecp_tables(name)
-        ctx.set_ecp(e.rn_local, e.local_coes, e.local_exps, e.rn_non_local, e.non_local_coes, e.non_local_exps, e.list_l)
+        ctx.set_ecp_tables(e)
         B = 4096 if dt == torch.float32 else 256
         pos = init_electrons(7, None, s.atoms, s.charges, s.spins, B, 1.0)[0].to("cuda", dt).contiguous()
         tag = f"{name}_{'f32' if dt == torch.float32 else 'f64'}"

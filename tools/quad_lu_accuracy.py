@@ -13,7 +13,6 @@ from aiqmc import _lib  # noqa: E402
 
 for name in ("C_ecp", "C2_ecp"):
     s = system.make_system(name)
-    t = s.tables()
     e = {"C_ecp": pp.c_atom_ccecp, "C2_ecp": pp.c2_ccecp}[name]()
     rng = np.random.default_rng(11)
     params = system.flatten_params(system.init_params(rng, s, randomize_aux=True))
@@ -21,9 +20,8 @@ for name in ("C_ecp", "C2_ecp"):
     rot = pp.haar_rotations(rng, 512)
     out = {}
     for dt in (torch.float64, torch.float32):
-        ctx = _lib.Context(s.nelectrons, s.natoms, s.nspins, s.atoms, s.charges, t["spin_up_indices"],
-                           t["spin_down_indices"], t["parallel_indices"], t["antiparallel_indices"], dtype=dt, device=0)
-        ctx.set_ecp(e.rn_local, e.local_coes, e.local_exps, e.rn_non_local, e.non_local_coes, e.non_local_exps, e.list_l)
+        ctx = _lib.Context.for_system(s, dt)
+        ctx.set_ecp_tables(e)
         ctx.set_params(params)
         p = torch.tensor(pos, device="cuda", dtype=dt)
         r = torch.tensor(rot, device="cuda", dtype=dt)

@@ -1,7 +1,9 @@
-// api_util.h -- what the C-ABI translation units (aiqmc.hip, observables.hip, loss.hip,
-// sr_gram.hip, shape.hip) share: the error return, the HIP error check and the prologue of the
-// entry points that take a context and a batch of positions, and the typed launch layer (by_dtype,
-// the grid helper and the KArgs builders).
+// api_util.h -- what every translation unit of the library shares (the context units aiqmc.hip,
+// dmc.hip, debug.hip, observables.hip, components.hip, density.hip and corrsamples.hip, the
+// context-free loss.hip, sr_gram.hip and blocking.hip, and shape.hip): the error return, the HIP
+// error check and the prologue of the entry points that take a context and a batch of positions,
+// and the typed launch layer (by_dtype, the grid helper and the KArgs builders).  What only the
+// context units call of one another is declared in host_shared.h.
 #pragma once
 #include <hip/hip_runtime.h>
 

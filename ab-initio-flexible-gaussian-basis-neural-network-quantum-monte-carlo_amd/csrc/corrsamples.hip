@@ -38,6 +38,7 @@
 
 #include "aiqmc.h"
 #include "api_util.h"
+#include "reduce.h"
 
 namespace {
 
@@ -155,31 +156,10 @@ __global__ __launch_bounds__(WARP_WG) void k_space_warp(const T* __restrict__ po
   if (logjac && q < nrows && e == 0) logjac[q] = s;
 }
 
-// ---- estimator levels
-__device__ __forceinline__ double corr_block_sum(double v, double* red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  const int w = threadIdx.x >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[w] = v;
-  __syncthreads();
-  double t = 0.0;
-  for (int k = 0; k < (int)(blockDim.x >> 6); ++k) t += red[k];
-  return t;
-}
-// the larger of two values, NaN if either is
-__device__ __forceinline__ double nan_max(double a, double b) { return a != a ? a : (b != b ? b : (b > a ? b : a)); }
-__device__ __forceinline__ double corr_block_max(double v, double* red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = nan_max(v, __shfl_xor(v, o));
-  const int w = threadIdx.x >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[w] = v;
-  __syncthreads();
-  double t = red[0];
-  for (int k = 1; k < (int)(blockDim.x >> 6); ++k) t = nan_max(t, red[k]);
-  return t;
-}
+// ---- estimator levels (sums and the maximum: reduce.h's butterfly-then-ordered form)
+using aq::block_max_nan;
+using aq::block_sum;
+using aq::nan_max;
 
 template <typename T>
 __device__ __forceinline__ double corr_lw(const T* la0, const T* la1, const T* lj, int64_t i) {
@@ -195,7 +175,7 @@ __global__ __launch_bounds__(1024) void k_corr_l1(const T* __restrict__ la0, con
   lj += (size_t)m * n;
   double v = -INFINITY;
   for (int64_t i = threadIdx.x; i < n; i += blockDim.x) v = nan_max(v, corr_lw(la0, la1, lj, i));
-  v = corr_block_max(v, red);
+  v = block_max_nan(v, red);
   if (threadIdx.x == 0) out[m] = v;
 }
 
@@ -218,10 +198,10 @@ __global__ __launch_bounds__(1024) void k_corr_l2(const T* __restrict__ la0, con
     swe += w * (double)e1[i];
     sw2 += w * w;
   }
-  s0 = corr_block_sum(s0, red);
-  sw = corr_block_sum(sw, red);
-  swe = corr_block_sum(swe, red);
-  sw2 = corr_block_sum(sw2, red);
+  s0 = block_sum(s0, red);
+  sw = block_sum(sw, red);
+  swe = block_sum(swe, red);
+  sw2 = block_sum(sw2, red);
   if (threadIdx.x == 0) {
     double* o = out + 5 * (size_t)m;
     o[0] = (double)n;
@@ -252,8 +232,8 @@ __global__ __launch_bounds__(1024) void k_corr_l3(const T* __restrict__ la0, con
     sd += d;
     sd2 += d * d;
   }
-  sd = corr_block_sum(sd, red);
-  sd2 = corr_block_sum(sd2, red);
+  sd = block_sum(sd, red);
+  sd2 = block_sum(sd2, red);
   if (threadIdx.x == 0) {
     out[2 * (size_t)m] = sd;
     out[2 * (size_t)m + 1] = sd2;

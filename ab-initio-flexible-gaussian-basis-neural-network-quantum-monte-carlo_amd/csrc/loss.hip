@@ -10,6 +10,9 @@
 
 #include "aiqmc.h"
 #include "api_util.h"
+#include "reduce.h"
+
+using aq::block_sum;   // every sum below: reduce.h's butterfly-then-ordered form
 
 // Energy statistics of one iteration (loss.py:206-208 through constants.pmean_stats), one
 // workgroup: out[0..3] = [sum |e - m|^2, n m, n m^2, n] in fp64 (m = the mean of these n
@@ -17,17 +20,6 @@
 // finalize (one rank) out[4..5] = [m, sum |e - m|^2 / n], the reference's two-pass values.
 // k_energy_stats_final forms them from a summed 4-vector after the all-reduce (Chan's
 // combination; products not contracted into FMAs, so one rank's between-term n m^2 - n m^2 is 0).
-__device__ __forceinline__ double block_sum_1024(double v, double* red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  const int w = threadIdx.x >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[w] = v;
-  __syncthreads();
-  double t = 0.0;
-  for (int k = 0; k < (int)(blockDim.x >> 6); ++k) t += red[k];
-  return t;
-}
 __device__ __forceinline__ void energy_stats_final(double* out) {
 #pragma clang fp contract(off)
   const double mean = out[1] / out[3];
@@ -43,13 +35,13 @@ __global__ __launch_bounds__(1024) void k_energy_stats(const T* __restrict__ e, 
   double a = 0.0;
   for (int64_t i = threadIdx.x; i < n; i += blockDim.x) a += (double)e[i];
   const double nn = (double)n;
-  const double m = block_sum_1024(a, red) / nn;
+  const double m = block_sum(a, red) / nn;
   double q = 0.0;
   for (int64_t i = threadIdx.x; i < n; i += blockDim.x) {
     const double d = (double)e[i] - m;
     q += d * d;
   }
-  q = block_sum_1024(q, red);
+  q = block_sum(q, red);
   if (threadIdx.x == 0) {
     out[0] = q;
     out[1] = nn * m;
@@ -90,8 +82,8 @@ __global__ __launch_bounds__(1024) void k_loss_weights(const T* __restrict__ er,
     a += (double)er[i];
     if (cplx) b += (double)ei[i];
   }
-  const double mr = block_sum_1024(a, red) / nn;
-  const double mi = cplx ? block_sum_1024(b, red) / nn : 0.0;
+  const double mr = block_sum(a, red) / nn;
+  const double mi = cplx ? block_sum(b, red) / nn : 0.0;
   double q = 0.0, tr = 0.0, ti = 0.0;
   for (int64_t i = threadIdx.x; i < n; i += blockDim.x) {
     const double dr = (double)er[i] - mr, di = cplx ? (double)ei[i] - mi : 0.0;
@@ -99,12 +91,12 @@ __global__ __launch_bounds__(1024) void k_loss_weights(const T* __restrict__ er,
     tr += fabs(dr);
     ti += fabs(di);
   }
-  const double var = block_sum_1024(q, red) / nn;
+  const double var = block_sum(q, red) / nn;
   const bool clipping = clip > 0.0;
   double lor = 0.0, hir = 0.0, loi = 0.0, hii = 0.0, dcr = mr, dci = mi;
   if (clipping) {
-    const double tvr = block_sum_1024(tr, red) / nn;
-    const double tvi = cplx ? block_sum_1024(ti, red) / nn : 0.0;
+    const double tvr = block_sum(tr, red) / nn;
+    const double tvi = cplx ? block_sum(ti, red) / nn : 0.0;
     lor = mr - clip * tvr;
     hir = mr + clip * tvr;
     loi = mi - clip * tvi;
@@ -119,8 +111,8 @@ __global__ __launch_bounds__(1024) void k_loss_weights(const T* __restrict__ er,
           si += y < loi ? loi : (y > hii ? hii : y);
         }
       }
-      dcr = block_sum_1024(sr, red) / nn;
-      dci = cplx ? block_sum_1024(si, red) / nn : 0.0;
+      dcr = block_sum(sr, red) / nn;
+      dci = cplx ? block_sum(si, red) / nn : 0.0;
     }
   }
   for (int64_t i = threadIdx.x; i < n; i += blockDim.x) {
@@ -181,15 +173,15 @@ __global__ __launch_bounds__(1024) void k_lossr_l1(const T* __restrict__ er, con
       z += y != 0.0 ? 1.0 : 0.0;
     }
   }
-  const double mr = block_sum_1024(a, red) / nn;
-  const double mi = cplx ? block_sum_1024(b, red) / nn : 0.0;
-  const double nz = cplx ? block_sum_1024(z, red) : 0.0;
+  const double mr = block_sum(a, red) / nn;
+  const double mi = cplx ? block_sum(b, red) / nn : 0.0;
+  const double nz = cplx ? block_sum(z, red) : 0.0;
   double q = 0.0;
   for (int64_t i = threadIdx.x; i < n; i += blockDim.x) {
     const double dr = (double)er[i] - mr, di = cplx ? (double)ei[i] - mi : 0.0;
     q += dr * dr + di * di;
   }
-  q = block_sum_1024(q, red);
+  q = block_sum(q, red);
   if (threadIdx.x == 0) {
 #pragma clang fp contract(off)
     L1[0] = q;
@@ -225,8 +217,8 @@ __global__ __launch_bounds__(1024) void k_lossr_l2(const T* __restrict__ er, con
     tr += fabs((double)er[i] - mr);
     if (cplx) ti += fabs((double)ei[i] - mi);
   }
-  tr = block_sum_1024(tr, red);
-  ti = cplx ? block_sum_1024(ti, red) : 0.0;
+  tr = block_sum(tr, red);
+  ti = cplx ? block_sum(ti, red) : 0.0;
   if (threadIdx.x == 0) {
     L2[0] = tr;
     L2[1] = ti;
@@ -262,8 +254,8 @@ __global__ __launch_bounds__(1024) void k_lossr_l3(const T* __restrict__ er, con
     if (cr) cr[i] = (T)xc;
     if (ci) ci[i] = (T)yc;
   }
-  sr = block_sum_1024(sr, red);
-  si = cplx ? block_sum_1024(si, red) : 0.0;
+  sr = block_sum(sr, red);
+  si = cplx ? block_sum(si, red) : 0.0;
   if (threadIdx.x == 0) {
     L3[0] = sr;
     L3[1] = si;

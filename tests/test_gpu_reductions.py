@@ -1,4 +1,5 @@
-"""The small fixed-order reduction kernels of csrc/aiqmc.hip against plain float64 references.
+"""The small fixed-order reduction kernels of csrc/dmc.hip and csrc/loss.hip (their block
+reductions: csrc/reduce.h) against plain float64 references.
 
 1. k_dmc_branch (stochastic comb, DMC/branch.py:10-33) against oracle.dmc.branch in its three
    regimes -- one weight per thread (n <= 1024), the blocked scan held in LDS (n <= 4096) and the
@@ -525,3 +526,98 @@ def test_loss_level_edge_batches(dtype):
     more, all energies equal."""
     from aiqmc import _lib
     _check_edges(_lib.loss_level, _final_hip(dtype), dtype, "cuda")
+
+
+# ----------------------------------------------------------------------------- 4. block_sum's stated order
+
+STATS_N = [1, 63, 64, 65, 1023, 1024, 1025, 4097]
+
+
+def _fma(a, b, c):
+    """a * b + c rounded once (exact rational arithmetic; int / int rounds correctly)."""
+    from fractions import Fraction
+    return float(Fraction(a) * Fraction(b) + Fraction(c))
+
+
+def _block_sum_replica(v):
+    """csrc/reduce.h block_sum for a block of 1024 as its comment states it: v[t] is thread t's
+    value; within each wave of 64 an xor butterfly over the lane offsets 32, 16, 8, 4, 2, 1, then
+    the 16 wave sums (lane 0's) added in ascending order starting from 0."""
+    w = np.asarray(v, dtype=np.float64).reshape(16, 64).copy()
+    lane = np.arange(64)
+    for o in (32, 16, 8, 4, 2, 1):
+        w = w + w[:, lane ^ o]
+    t = 0.0
+    for k in range(16):
+        t = t + float(w[k, 0])
+    return t
+
+
+def _per_thread(x):
+    """[1024] thread t's sequential double sum of x[t], x[t + 1024], ... from 0 (a missing element
+    is a + 0.0 = a)."""
+    pad = np.zeros(-(-x.size // 1024) * 1024)
+    pad[:x.size] = x
+    a = np.zeros(1024)
+    for row in pad.reshape(-1, 1024):
+        a = a + row
+    return a
+
+
+def _energy_stats_replica(x):
+    """k_energy_stats (csrc/loss.hip, one block of 1024, finalize on) on the float64 array x:
+    m = block_sum(per-thread sums) / n; the second pass the same on (e - m)^2, each thread's
+    q += d * d being one fused multiply-add (the device compiler's default contraction; the
+    compiled loop is v_add_f64, v_fmac_f64); out = [q, n m, (n m) m, n, m, q / n]."""
+    nn = float(x.size)
+    s = _block_sum_replica(_per_thread(x))
+    m = s / nn
+    q = [0.0] * 1024
+    for i, e in enumerate(x.tolist()):
+        d = e - m
+        q[i % 1024] = _fma(d, d, q[i % 1024])
+    qq = _block_sum_replica(q)
+    return s, q, np.array([qq, nn * m, nn * m * m, nn, m, qq / nn])
+
+
+# seeds at which the kernel's order and the exactly rounded sum give different bits (searched on
+# the CPU, see test_energy_stats_bitwise_stated_order); 900 + n where not listed
+STATS_SEED = {("f32", 63): 20963, ("f32", 64): 70964, ("f32", 65): 30965, ("f32", 1023): 821923, ("f32", 1024): 341924, ("f32", 1025): 1521925, ("f64", 63): 10963,
+              ("f64", 64): 30964, ("f64", 1023): 11923, ("f64", 1025): 11925}
+
+
+def _stats_input(n, dtype):
+    """Both signs, magnitudes log-uniform over 1e-3 .. 1e5, rounded to dtype: a changed summation
+    order changes the last bits."""
+    rng = np.random.default_rng(STATS_SEED.get((DT_IDS[DTYPES.index(dtype)], n), 900 + n))
+    x = rng.choice([-1.0, 1.0], n) * 10.0 ** rng.uniform(-3.0, 5.0, n)
+    return x.astype(NP_DT[dtype]).astype(np.float64)
+
+
+@pytest.mark.parametrize("n", STATS_N)
+@pytest.mark.parametrize("dtype", DTYPES, ids=DT_IDS)
+def test_energy_stats_bitwise_stated_order(dtype, n):
+    """aiqmc_energy_stats (finalize on) bit for bit against a host replica written from
+    csrc/reduce.h's comment on block_sum: a partial wave, one wave, a wave boundary, a partial
+    block, a full one and more than one element per thread.  The replica is first shown to differ
+    from the exactly rounded sum (math.fsum) of the same numbers, so that the comparison can see a
+    changed order: in the first pass (the sum of the energies) for every n > 1, except the
+    float32 inputs with n <= 65, whose double sums are exact in any order (24-bit numbers between
+    2^-10 and 2^17, at most 65 of them: under 53 bits) -- there in the second pass, the sum of
+    the rounded (e - m)^2.  n = 1 has one term and no order."""
+    import math
+    from aiqmc import _lib
+    x = _stats_input(n, dtype)
+    s, q, want = _energy_stats_replica(x)
+    exact, qexact = math.fsum(x.tolist()), math.fsum(q)
+    print(n, "replica sum", repr(s), "fsum", repr(exact), "second pass", repr(want[0]), "fsum", repr(qexact))
+    if n > 1 and (dtype == torch.float64 or n > 65):
+        assert s != exact and abs(s - exact) <= 2.0 ** -45 * float(np.abs(x).sum())
+    elif n > 1:
+        assert s == exact and want[0] != qexact and abs(want[0] - qexact) <= 2.0 ** -45 * qexact
+    got = _lib.energy_stats(torch.tensor(x, dtype=dtype, device="cuda"), finalize=True)
+    torch.cuda.synchronize()
+    g = got.cpu().numpy()
+    print("  replica", want.tolist())
+    print("  kernel ", g.tolist())
+    assert g.tobytes() == want.tobytes()

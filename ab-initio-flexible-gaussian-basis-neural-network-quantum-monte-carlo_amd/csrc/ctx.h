@@ -10,6 +10,7 @@
 
 #include "aiqmc.h"
 #include "devbuf.h"
+#include "param_map.h"
 #include "walker_kernel.h"
 
 using aq::KArgs;
@@ -20,7 +21,10 @@ struct aiqmc_ctx {
   int npar = 0, nanti = 0;
   std::vector<double> atoms, charges;
   std::vector<int> up, dn, par, anti;
-  int64_t ncanon = 0, nkern = 0, nprm = 0;   // nprm: device parameter buffer (nkern + lane-order copies)
+  // the canonical <-> kernel-layout parameter map (param_map.h), built once by aiqmc_create: the
+  // program of both parameter uploads and the index map of the parameter gradient
+  ParamMap pmap;
+  int64_t ncanon = 0, nkern = 0, nprm = 0;   // pmap's; nprm: device parameter buffer (nkern + lane-order copies)
   // Device memory: every buffer is a DevBuf (devbuf.h), sized where it is used by reserve() and
   // freed with the context.  aiqmc_workspace_bytes counts the groups marked [counted].
   DevBuf d_prm, d_rowsrc;
@@ -60,9 +64,9 @@ struct aiqmc_ctx {
   DevBuf d_tm_scr;                 // T-moves per-walker amplitudes [B][N*A*50][4]
   DevBuf d_dscr;                   // DMC reduction scratch: block partial sums / cut minima [2*64]
   // parameter gradients (aiqmc_logpsi_param_grad, walker_pgrad.h)
-  DevBuf d_gmap;                   // int [ncanon]
+  DevBuf d_gmap;                   // int [ncanon] pmap.gmap, uploaded on first use
   DevBuf d_wnorm;                  // double [6] |W_y row| of the current parameters
-  // device repack program of aiqmc_set_params_device (built once per context from pack_params):
+  // device copy of pmap.op / src / cval [nprm], uploaded by the first aiqmc_set_params_device:
   // per kernel-layout entry an op (0 constant, 1 copy, 2 row-normalised y coefficient), its
   // canonical source index and its constant value
   DevBuf d_pk_op, d_pk_src, d_pk_cval;
@@ -94,13 +98,8 @@ struct ShapeOps {
   void (*phase_read)(unsigned long long* out32);               // AQ_PHASE_PROF builds only
   int wcache_n, ecache_n;                                      // cache entries per walker / per proposal
   int lcache_n;                                                // LapCache entries per walker
-  int64_t nkern;
-  int64_t nprm;
-  long (*ncanon)(int npar, int nanti);
-  void (*pack)(const aiqmc_ctx* c, const double* flat, std::vector<double>& out);
-  void (*gmap)(const aiqmc_ctx* c, std::vector<int>& map);                        // canonical -> kernel index
-  int (*pgrad)(int dtype, const KArgs& ka, int nconf, hipStream_t s);            // k_param_grad
-  int wy_off;                                                                      // Lay::wy
+  void (*param_map)(const aiqmc_ctx* c, ParamMap& m);          // build_param_map from the context's tables
+  int (*pgrad)(int dtype, const KArgs& ka, int nconf, hipStream_t s);   // k_param_grad
   // dynamic LDS bytes per workgroup of the launches that take it, [dtype f32, f64][kind]
   // (kind: AIQMC_LDS_* of aiqmc.h), and the waves per workgroup of each: what a profiler's
   // dispatch record does not show (rocprofv3 reports the static group segment only)

@@ -1,11 +1,14 @@
 // layout.h -- kernel-side parameter layout for the AIQMC network (N electrons,
 // A atoms, two occupied spin channels, default hidden dims).
 //
-// The host repacks the canonical tree_flatten parameter vector (see
-// include/aiqmc.h) into this layout once per aiqmc_set_params; derived
-// quantities (row-normalised y coefficients nn.py:449-451, (2Z)^{3/4},
-// (2Z)^{1/4} Jastrow.py:95, e-e cusp/alpha tables Jastrow.py:23-41, V_nn)
-// are precomputed there in double precision.
+// The canonical tree_flatten parameter vector (see include/aiqmc.h) is
+// repacked into this layout once per aiqmc_set_params (on the host) or
+// aiqmc_set_params_device (on the device).  Which canonical parameter each
+// entry holds, the canonical order and count, and the derived quantities
+// (row-normalised y coefficients nn.py:449-451, (2Z)^{3/4}, (2Z)^{1/4}
+// Jastrow.py:95, e-e cusp/alpha tables Jastrow.py:23-41, V_nn, precomputed in
+// double precision) are stated once, in param_map.h; this file says only
+// where an entry sits.
 #pragma once
 
 namespace aq {
@@ -96,19 +99,6 @@ struct Lay {
   static constexpr int total_ext = xcb(3);   // device parameter buffer
   static_assert(Q0 <= XQ && Q1 <= XQ, "conv outputs exceed the padded lane records");
   static_assert(CBN(Q0) <= XB && CBN(Q1) <= XB, "conv bias record");
-
-  // canonical (tree_flatten) parameter count
-  static constexpr long canon(int npar, int nanti) {
-    return (long)N * (2 + 12 * A)                       // envelope
-           + (long)N * A                                // jastrow_ae
-           + npar + nanti                               // jastrow_ee
-           + (N * Q0 + N * D0) + (NH2 + NH2 * NH2) + (NH + Q0 * NH)   // streams[0]
-           + (N * Q1 + N * D1) + (NH2 + NH2 * NH2) + (NH + Q1 * NH)   // streams[1]
-           + (N * Q1 + N * D1) + (NH + Q1 * NH)                        // streams[2]
-           + (NYW + DY0 * NYW) + 2 * (NYW + NYW * NYW)                 // streams_y
-           + 2 * (2 * N + NH * 2 * N)                                  // orbitals
-           + NYW * N;                                                  // y
-  }
 };
 
 // Per-walker cache of the local-energy launch pair (walker_lap.h): written by the

@@ -37,199 +37,10 @@ __global__ __launch_bounds__(256) void k_accept(T* __restrict__ pos, AccArgs a, 
   }
 }
 
+// the canonical <-> kernel-layout parameter map of this shape (param_map.h) from the context's tables
 template <int N, int A>
-static void pack_params(const aiqmc_ctx* c, const double* flat, std::vector<double>& out) {
-  using Ly = Lay<N, A>;
-  out.assign(Ly::total_ext, 0.0);
-  const double* p = flat;
-  auto take = [&](int n) {
-    const double* q = p;
-    p += n;
-    return q;
-  };
-  // envelope[i]: alpha, beta, eplion, mu, nu, pi, sigma, xi (sorted keys)
-  for (int i = 0; i < N; ++i) {
-    const double* alpha = take(1);
-    const double* beta = take(A);
-    take(3 * A);   // eplion (unused by envelope.apply)
-    take(A);       // mu
-    take(A);       // nu
-    const double* pi = take(3 * A);
-    const double* sigma = take(3 * A);
-    const double* xi = take(1);
-    out[Ly::env_alpha + i] = alpha[0];
-    out[Ly::env_xi + i] = xi[0];
-    for (int a = 0; a < A; ++a) {
-      out[Ly::env_beta + i * A + a] = beta[a];
-      for (int d = 0; d < 3; ++d) {
-        out[Ly::env_pi + (i * A + a) * 3 + d] = pi[a * 3 + d];
-        out[Ly::env_sigma + (i * A + a) * 3 + d] = sigma[a * 3 + d];
-      }
-    }
-  }
-  const double* jae = take(N * A);
-  for (int k = 0; k < N * A; ++k) out[Ly::jae_b + k] = jae[k];
-  const double* ee_anti = take(c->nanti);
-  const double* ee_par = take(c->npar);
-  for (int q = 0; q < c->npar; ++q) {
-    const int i = c->par[q], j = c->par[c->npar + q];
-    out[Ly::jee_c + i * N + j] = out[Ly::jee_c + j * N + i] = 0.25;
-    out[Ly::jee_a + i * N + j] = out[Ly::jee_a + j * N + i] = ee_par[q];
-  }
-  for (int q = 0; q < c->nanti; ++q) {
-    const int i = c->anti[q], j = c->anti[c->nanti + q];
-    out[Ly::jee_c + i * N + j] = out[Ly::jee_c + j * N + i] = 0.5;
-    out[Ly::jee_a + i * N + j] = out[Ly::jee_a + j * N + i] = ee_anti[q];
-  }
-  // layers.input = {} ; layers.streams[l] = {convolutional{b,w}, double{b,w}, single{b,w}}
-  const int D[3] = {Ly::D0, Ly::D1, Ly::D1};
-  const int Q[3] = {Ly::Q0, Ly::Q1, Ly::Q1};
-  const int cw[3] = {Ly::conv_w0, Ly::conv_w1, Ly::conv_w2};
-  const int cb[3] = {Ly::conv_b0, Ly::conv_b1, Ly::conv_b2};
-  const int sw[3] = {Ly::sng_w0, Ly::sng_w1, Ly::sng_w2};
-  const int sb[3] = {Ly::sng_b0, Ly::sng_b1, Ly::sng_b2};
-  const int dw[2] = {Ly::dbl_w0, Ly::dbl_w1};
-  const int db[2] = {Ly::dbl_b0, Ly::dbl_b1};
-  for (int l = 0; l < 3; ++l) {
-    const double* b = take(N * Q[l]);
-    const double* w = take(N * D[l]);
-    for (int k = 0; k < N * Q[l]; ++k) out[cb[l] + k] = b[k];
-    for (int k = 0; k < N * D[l]; ++k) out[cw[l] + k] = w[k];
-    if (l < 2) {
-      const double* bb = take(NH2);
-      const double* ww = take(NH2 * NH2);
-      for (int k = 0; k < NH2; ++k) out[db[l] + k] = bb[k];
-      for (int k = 0; k < NH2 * NH2; ++k) out[dw[l] + k] = ww[k];
-    }
-    const double* sbp = take(NH);
-    const double* swp = take(Q[l] * NH);
-    for (int k = 0; k < NH; ++k) out[sb[l] + k] = sbp[k];
-    for (int k = 0; k < Q[l] * NH; ++k) out[sw[l] + k] = swp[k];
-  }
-  // lane-order copies of the h-stream weights (layout.h x* blocks)
-  for (int l = 0; l < 3; ++l) {
-    const int QF = Q[l] / 4;
-    for (int i = 0; i < N; ++i)
-      for (int f = 0; f < 4; ++f) {
-        for (int q = 0; q < Q[l]; ++q) out[Ly::xcw(l) + (i * 4 + f) * Ly::XQ + q] = out[cw[l] + i * D[l] + 4 * q + f];
-        for (int s4 = 0; s4 < QF; ++s4) out[Ly::xcb(l) + (i * 4 + f) * Ly::XB + s4] = out[cb[l] + i * Q[l] + 4 * s4 + f];
-        for (int q = 4 * QF; q < Q[l]; ++q) out[Ly::xcb(l) + (i * 4 + f) * Ly::XB + QF + q - 4 * QF] = out[cb[l] + i * Q[l] + q];
-      }
-    for (int f = 0; f < 4; ++f)
-      for (int q = 0; q < Q[l]; ++q) out[Ly::xsw(l) + f * Ly::XQ + q] = out[sw[l] + q * NH + f];
-    for (int q = 0; q < Q[l]; ++q)
-      for (int f = 0; f < 4; ++f) out[Ly::xsr(l) + q * 4 + f] = out[sw[l] + q * NH + f];
-  }
-  // layers.streams_y[l].single_Ynlm {b, w}
-  const int yin[3] = {Ly::DY0, NYW, NYW};
-  const int yw[3] = {Ly::y_w0, Ly::y_w1, Ly::y_w2};
-  const int yb[3] = {Ly::y_b0, Ly::y_b1, Ly::y_b2};
-  for (int l = 0; l < 3; ++l) {
-    const double* b = take(NYW);
-    const double* w = take(yin[l] * NYW);
-    for (int k = 0; k < NYW; ++k) out[yb[l] + k] = b[k];
-    for (int k = 0; k < yin[l] * NYW; ++k) out[yw[l] + k] = w[k];
-  }
-  // orbitals[s] {b [2N], w [4][2N]} ; complex = even + i odd (nn.py:456)
-  for (int s = 0; s < 2; ++s) {
-    const double* b = take(2 * N);
-    const double* w = take(NH * 2 * N);
-    for (int col = 0; col < N; ++col) {
-      out[Ly::orb_b + (s * N + col) * 2 + 0] = b[2 * col];
-      out[Ly::orb_b + (s * N + col) * 2 + 1] = b[2 * col + 1];
-      for (int f = 0; f < NH; ++f) {
-        out[Ly::orb_w + ((s * NH + f) * N + col) * 2 + 0] = w[f * 2 * N + 2 * col];
-        out[Ly::orb_w + ((s * NH + f) * N + col) * 2 + 1] = w[f * 2 * N + 2 * col + 1];
-      }
-    }
-  }
-  // y[0].w [6][N], row-normalised (nn.py:449-451)
-  const double* wy = take(NYW * N);
-  for (int m = 0; m < NYW; ++m) {
-    double nrm = 0.0;
-    for (int col = 0; col < N; ++col) nrm += wy[m * N + col] * wy[m * N + col];
-    nrm = std::sqrt(nrm);
-    for (int col = 0; col < N; ++col) out[Ly::wy + m * N + col] = wy[m * N + col] / nrm;
-  }
-  // system constants
-  for (int a = 0; a < A; ++a) {
-    for (int d = 0; d < 3; ++d) out[Ly::atoms + a * 3 + d] = c->atoms[a * 3 + d];
-    out[Ly::charges + a] = c->charges[a];
-    out[Ly::c34 + a] = std::pow(2.0 * c->charges[a], 0.75);
-    out[Ly::c14 + a] = std::pow(2.0 * c->charges[a], 0.25);
-  }
-  double vnn = 0.0;
-  for (int a = 0; a < A; ++a)
-    for (int b = a + 1; b < A; ++b) {
-      double r2 = 0.0;
-      for (int d = 0; d < 3; ++d) {
-        const double t = c->atoms[a * 3 + d] - c->atoms[b * 3 + d];
-        r2 += t * t;
-      }
-      vnn += c->charges[a] * c->charges[b] / std::sqrt(r2);
-    }
-  out[Ly::vnn] = vnn;
-}
-
-// Canonical (tree_flatten) index -> kernel-layout index of the same parameter, the transpose of
-// pack_params (see k_grad_canon for the -1 / <= -2 codes).
-template <int N, int A>
-static void gmap_impl(const aiqmc_ctx* c, std::vector<int>& map) {
-  using Ly = Lay<N, A>;
-  map.clear();
-  auto put = [&](int k) { map.push_back(k); };
-  for (int i = 0; i < N; ++i) {
-    put(Ly::env_alpha + i);
-    for (int a = 0; a < A; ++a) put(Ly::env_beta + i * A + a);
-    for (int k = 0; k < 3 * A; ++k) put(-1);   // eplion
-    for (int k = 0; k < A; ++k) put(-1);       // mu
-    for (int k = 0; k < A; ++k) put(-1);       // nu
-    for (int k = 0; k < 3 * A; ++k) put(Ly::env_pi + i * A * 3 + k);
-    for (int k = 0; k < 3 * A; ++k) put(Ly::env_sigma + i * A * 3 + k);
-    put(Ly::env_xi + i);
-  }
-  for (int k = 0; k < N * A; ++k) put(Ly::jae_b + k);
-  auto pairs = [&](const std::vector<int>& t, int n) {
-    for (int q = 0; q < n; ++q) {
-      const int i = t[q], j = t[n + q];
-      put(Ly::jee_a + (i < j ? i * N + j : j * N + i));
-    }
-  };
-  pairs(c->anti, c->nanti);
-  pairs(c->par, c->npar);
-  const int D[3] = {Ly::D0, Ly::D1, Ly::D1};
-  const int Q[3] = {Ly::Q0, Ly::Q1, Ly::Q1};
-  const int cw[3] = {Ly::conv_w0, Ly::conv_w1, Ly::conv_w2};
-  const int cb[3] = {Ly::conv_b0, Ly::conv_b1, Ly::conv_b2};
-  const int sw[3] = {Ly::sng_w0, Ly::sng_w1, Ly::sng_w2};
-  const int sb[3] = {Ly::sng_b0, Ly::sng_b1, Ly::sng_b2};
-  const int dw[2] = {Ly::dbl_w0, Ly::dbl_w1};
-  const int db[2] = {Ly::dbl_b0, Ly::dbl_b1};
-  for (int l = 0; l < 3; ++l) {
-    for (int k = 0; k < N * Q[l]; ++k) put(cb[l] + k);
-    for (int k = 0; k < N * D[l]; ++k) put(cw[l] + k);
-    if (l < 2) {
-      for (int k = 0; k < NH2; ++k) put(db[l] + k);
-      for (int k = 0; k < NH2 * NH2; ++k) put(dw[l] + k);
-    }
-    for (int k = 0; k < NH; ++k) put(sb[l] + k);
-    for (int k = 0; k < Q[l] * NH; ++k) put(sw[l] + k);
-  }
-  const int yin[3] = {Ly::DY0, NYW, NYW};
-  const int yw[3] = {Ly::y_w0, Ly::y_w1, Ly::y_w2};
-  const int yb[3] = {Ly::y_b0, Ly::y_b1, Ly::y_b2};
-  for (int l = 0; l < 3; ++l) {
-    for (int k = 0; k < NYW; ++k) put(yb[l] + k);
-    for (int k = 0; k < yin[l] * NYW; ++k) put(yw[l] + k);
-  }
-  for (int sp = 0; sp < 2; ++sp) {
-    for (int k = 0; k < 2 * N; ++k) put(Ly::orb_b + (sp * N + k / 2) * 2 + (k & 1));
-    for (int k = 0; k < NH * 2 * N; ++k) {
-      const int f = k / (2 * N), r = k - f * 2 * N;
-      put(Ly::orb_w + ((sp * NH + f) * N + r / 2) * 2 + (r & 1));
-    }
-  }
-  for (int k = 0; k < NYW * N; ++k) put(-2 - k);
+static void param_map_impl(const aiqmc_ctx* c, ParamMap& m) {
+  build_param_map<N, A>(c->npar, c->nanti, c->par.data(), c->anti.data(), c->atoms.data(), c->charges.data(), m);
 }
 
 // hipFuncSetAttribute for a launch that takes more dynamic LDS than the default 64 KB limit
@@ -449,13 +260,8 @@ bool AQ_CAT(AQ_N, AQ_A)(ShapeOps* ops) {
   ops->phase_read = &phase_read_impl;
   ops->wcache_n = WCache<AQ_N, AQ_A>::size;
   ops->ecache_n = ECache<AQ_N, AQ_A>::size;
-  ops->nkern = Lay<AQ_N, AQ_A>::total;
-  ops->nprm = Lay<AQ_N, AQ_A>::total_ext;
-  ops->ncanon = &Lay<AQ_N, AQ_A>::canon;
-  ops->pack = &pack_params<AQ_N, AQ_A>;
-  ops->gmap = &gmap_impl<AQ_N, AQ_A>;
+  ops->param_map = &param_map_impl<AQ_N, AQ_A>;
   ops->pgrad = &pgrad_impl<AQ_N, AQ_A>;
-  ops->wy_off = Lay<AQ_N, AQ_A>::wy;
   launch_table<float, AQ_N, AQ_A>(ops->dyn_lds[0], ops->wg_waves[0]);
   launch_table<double, AQ_N, AQ_A>(ops->dyn_lds[1], ops->wg_waves[1]);
   return true;

@@ -645,7 +645,7 @@ __global__ __launch_bounds__(256) void k_grad_final(const T* __restrict__ part, 
 }
 
 // Kernel layout -> canonical (tree_flatten) order for `rows` gradient vectors.  map[k] >= 0: the
-// kernel entry of canonical parameter k; -1: unused by the network (eplion, mu, nu, envelope.py);
+// kernel entry of canonical parameter k; -1: an envelope leaf the network does not read (envelope.py);
 // <= -2: the y coefficient W_y[m][c] (m*N + c = -2 - map[k]), whose kernel entry is the
 // row-normalised What = W / |W_m| (nn.py:449-451): dW = (dWhat - What (What . dWhat)) / |W_m|.
 template <typename T>

@@ -94,7 +94,27 @@ DENSITY_FIELDS = ("total", "skipped", "grid", "grid_out", "radial", "radial_out"
 BLOCKING_MAX_SERIES = 8        # AIQMC_BLOCKING_MAX_SERIES
 BLOCKING_MAX_LEVELS = 32       # AIQMC_BLOCKING_MAX_LEVELS
 # rows of aiqmc_energy_components, in the order of the AIQMC_COMP_* macros (AIQMC_NCOMPONENTS = 8)
+RDM_GROUP = 32                 # AIQMC_RDM_GROUP: walkers per contraction workgroup (aiqmc_rdm_accumulate)
+RDM_MAX_AO, RDM_MAX_ORB, RDM_MAX_PRIM, RDM_MAX_Q = 128, 64, 512, 16   # AIQMC_RDM_MAX_*
 COMPONENT_NAMES = ("total", "kinetic", "kinetic_grad", "v_ee", "v_en", "v_nn", "v_pp_local", "v_pp_nonlocal")
+
+
+class AiqmcRdmBasis(ctypes.Structure):
+    """aiqmc_rdm_basis: shells, optional MO coefficients and the mixture q."""
+    _fields_ = [
+        ("nshell", ctypes.c_int32),
+        ("shell_l", ctypes.POINTER(ctypes.c_int32)),
+        ("shell_nprim", ctypes.POINTER(ctypes.c_int32)),
+        ("shell_center", ctypes.POINTER(ctypes.c_double)),
+        ("exps", ctypes.POINTER(ctypes.c_double)),
+        ("coefs", ctypes.POINTER(ctypes.c_double)),
+        ("norb", ctypes.c_int32),
+        ("mo_coeff", ctypes.POINTER(ctypes.c_double)),
+        ("nq", ctypes.c_int32),
+        ("q_center", ctypes.POINTER(ctypes.c_double)),
+        ("q_sigma", ctypes.POINTER(ctypes.c_double)),
+        ("q_prob", ctypes.POINTER(ctypes.c_double)),
+    ]
 
 
 def density_cfg(grid=None, radial=None, pair=None) -> AiqmcDensityCfg:
@@ -154,6 +174,9 @@ _SIGNATURES = {
     "aiqmc_energy_components": (_int, [_vp, _vp, _i32, _i32, _i32, _vp, _u64, _u64, _vp, _vp]),
     "aiqmc_density_layout": (_int, [_vp, _p(AiqmcDensityCfg), _p(_i64), _p(_i64), _p(_i32)]),
     "aiqmc_density_accumulate": (_int, [_vp, _p(AiqmcDensityCfg), _vp, _i32, _vp, _vp, _vp]),
+    "aiqmc_set_rdm_basis": (_int, [_vp, _p(AiqmcRdmBasis)]),
+    "aiqmc_rdm_accumulate": (_int, [_vp, _vp, _i32, _i32, _i32, _vp, _u64, _u64, _vp, _vp, _i32, _vp, _vp, _vp]),
+    "aiqmc_rdm_basis_values": (_int, [_vp, _vp, _i32, _i32, _vp, _vp]),
     "aiqmc_space_warp": (_int, [_vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp]),
     "aiqmc_corr_level": (_int, [_i32, _i32, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "aiqmc_corr_final": (_int, [_vp, _vp, _i32, _vp, _vp]),
@@ -730,6 +753,107 @@ class Context:
             check(self._lib.aiqmc_density_accumulate(self._h, ctypes.byref(cfg), _ptr(p), B, _ptr(w), _ptr(acc),
                                                      _stream(self.device)), "aiqmc_density_accumulate")
         return acc
+
+    # -- one-body density matrix (aiqmc/observables.py make_density_matrix) ------
+    def set_rdm_basis(self, shell_l, shell_nprim, shell_center, exps, coefs, mo_coeff, q_center, q_sigma, q_prob,
+                      token=None) -> None:
+        """aiqmc_set_rdm_basis: shells (l [nshell], primitives per shell [nshell], centres
+        [nshell, 3], concatenated exponents and coefficients), mo_coeff [2, nao, norb] or None (the
+        functions themselves) and the mixture q (centres [nq, 3], sigmas, probabilities).  token:
+        anything comparable that identifies these tables; a call with the token of the tables
+        already uploaded does nothing."""
+        if token is not None and token == getattr(self, "_rdm_token", None):
+            return
+        i32 = lambda a: np.ascontiguousarray(np.asarray(a, dtype=np.int32).reshape(-1))
+        dbl = lambda a: np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape(-1))
+        pi = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
+        pd = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+        l, npr, cen, ex, co = i32(shell_l), i32(shell_nprim), dbl(shell_center), dbl(exps), dbl(coefs)
+        qc, qs, qp = dbl(q_center), dbl(q_sigma), dbl(q_prob)
+        nao = int(((l + 1) * (l + 2) // 2).sum())
+        if cen.size != 3 * l.size or npr.size != l.size or ex.size != co.size or ex.size != int(npr.sum()):
+            raise ValueError("set_rdm_basis: shell tables of inconsistent sizes")
+        if qc.size != 3 * qs.size or qp.size != qs.size:
+            raise ValueError("set_rdm_basis: q tables of inconsistent sizes")
+        b = AiqmcRdmBasis()
+        b.nshell, b.shell_l, b.shell_nprim, b.shell_center, b.exps, b.coefs = l.size, pi(l), pi(npr), pd(cen), pd(ex), pd(co)
+        mo = None
+        if mo_coeff is not None:
+            mo = np.asarray(mo_coeff, dtype=np.float64)
+            if mo.ndim != 3 or mo.shape[0] != 2 or mo.shape[1] != nao:
+                raise ValueError(f"set_rdm_basis: mo_coeff must be [2, nao={nao}, norb]")
+            b.norb = mo.shape[2]
+            mo = np.ascontiguousarray(mo.reshape(-1))
+            b.mo_coeff = pd(mo)
+        else:
+            b.norb = nao
+        b.nq, b.q_center, b.q_sigma, b.q_prob = qs.size, pd(qc), pd(qs), pd(qp)
+        self._rdm_token = None
+        with torch.cuda.device(self.device):
+            check(self._lib.aiqmc_set_rdm_basis(self._h, ctypes.byref(b)), "aiqmc_set_rdm_basis")
+        self._rdm_token, self.rdm_norb = token, int(b.norb)
+
+    def clear_rdm_basis(self) -> None:
+        self._rdm_token = None
+        check(self._lib.aiqmc_set_rdm_basis(self._h, None), "aiqmc_set_rdm_basis")
+
+    def rdm_basis_values(self, points: torch.Tensor, spin: int = 0) -> torch.Tensor:
+        """aiqmc_rdm_basis_values: the basis functions (MO-contracted with spin's coefficients when
+        set) at points [M, 3] -> [M, norb] of the context dtype."""
+        p = torch.as_tensor(points).to(self.device, self.dtype).contiguous().reshape(-1, 3)
+        M = p.shape[0]
+        K = int(getattr(self, "rdm_norb", 0))
+        out = torch.empty(M, K, dtype=self.dtype, device=self.device)
+        with torch.cuda.device(self.device):
+            check(self._lib.aiqmc_rdm_basis_values(self._h, _ptr(p), M, int(spin), _ptr(out), _stream(self.device)),
+                  "aiqmc_rdm_basis_values")
+        return out
+
+    def rdm_accumulate(self, pos: torch.Tensor, samples: int, rprime: Optional[torch.Tensor] = None, seed: int = 0,
+                       step: int = 0, weights: Optional[torch.Tensor] = None, acc: Optional[torch.Tensor] = None,
+                       accumulate: bool = False, want_points: bool = False, want_ratios: bool = False,
+                       chunk: Optional[int] = None):
+        """aiqmc_rdm_accumulate: acc (float64 [1 + 2 K K 2] on this device; None: a new one) receives
+        W = sum of the weights and the sums [2, K, K, (re, im)] over walkers, points and electrons of
+        the channel; accumulate adds into acc.  rprime [B, S, 3]: the injected points (None: drawn
+        from q by Philox (seed, step)).  Returns acc, then rprime_out [B, S, 3] (want_points) and
+        ratio_out [B, S, N, 2] (want_ratios).  chunk: as in spin_squared.  No host synchronisation."""
+        p = self._pos(pos)
+        B, S = p.shape[0], int(samples)
+        K = int(getattr(self, "rdm_norb", 0))
+        n = 1 + 4 * K * K
+        if acc is None:
+            acc = torch.zeros(n, dtype=torch.float64, device=self.device)
+        elif not (isinstance(acc, torch.Tensor) and acc.dtype == torch.float64 and acc.device == self.device
+                  and acc.is_contiguous() and acc.numel() == n):
+            raise ValueError(f"rdm_accumulate: acc must be a contiguous float64 tensor of {n} entries on {self.device}")
+        r = None
+        if rprime is not None:
+            r = torch.as_tensor(rprime).to(self.device, self.dtype).contiguous()
+            if r.numel() != B * max(S, 0) * 3:
+                raise ValueError("rprime must be [B, S, 3]")
+        w = None
+        if weights is not None:
+            w = torch.as_tensor(weights).to(self.device, self.dtype).contiguous().reshape(-1)
+            if w.numel() != B:
+                raise ValueError("weights must have one entry per walker")
+        rp = torch.empty(B, max(S, 0), 3, dtype=self.dtype, device=self.device) if want_points else None
+        ro = torch.empty(B, max(S, 0), self.N, 2, dtype=self.dtype, device=self.device) if want_ratios else None
+        if chunk is not None:
+            if int(chunk) <= 0:
+                raise ValueError("chunk must be positive")
+            check(self._lib.aiqmc_debug_set_obs_chunk(self._h, int(chunk)), "aiqmc_debug_set_obs_chunk")
+        try:
+            with torch.cuda.device(self.device):
+                check(self._lib.aiqmc_rdm_accumulate(
+                    self._h, _ptr(p), B, S, AIQMC_RNG_HOST if r is not None else AIQMC_RNG_PHILOX, _ptr(r),
+                    ctypes.c_uint64(seed), ctypes.c_uint64(step), _ptr(w), _ptr(acc), 1 if accumulate else 0, _ptr(rp),
+                    _ptr(ro), _stream(self.device)), "aiqmc_rdm_accumulate")
+        finally:
+            if chunk is not None:
+                self._lib.aiqmc_debug_set_obs_chunk(self._h, 0)
+        out = (acc,) + ((rp,) if want_points else ()) + ((ro,) if want_ratios else ())
+        return out if len(out) > 1 else acc
 
     # -- correlated sampling (aiqmc/correlatedsamples) ------------------------
     def space_warp(self, pos: torch.Tensor, new_atoms):

@@ -76,6 +76,18 @@ struct aiqmc_ctx {
   // configurations [n][3N], their log|psi| and phase [n], and the value launch's walker cache
   DevBuf d_obs_x, d_obs_lp, d_obs_ph, d_obs_wc;
   int obs_chunk = 4096;              // configurations per value launch (aiqmc_debug_set_obs_chunk)
+  // one-body density matrix (aiqmc_set_rdm_basis / aiqmc_rdm_accumulate, rdm.hip).  The tables
+  // are the context's, as the ECP table is: d_rdm_tab doubles (shell centres [nshell][3], primitive
+  // exponents and coefficients [nprim] each, MO coefficients [2][nao][norb] when rdm_mo, then q:
+  // centres [nq][3], 1 / (2 sigma^2), p (2 pi sigma^2)^-3/2, sigma, cumulative p: [nq] each),
+  // d_rdm_shell ints [nshell][4] = (l, first primitive, primitives, first function)
+  bool rdm_set = false, rdm_mo = false;
+  int rdm_nshell = 0, rdm_nprim = 0, rdm_nao = 0, rdm_norb = 0, rdm_nq = 0;
+  DevBuf d_rdm_tab, d_rdm_shell;
+  // its chunk workspace beside d_obs_*: points r' [W][S][3] and 1/q [W][S], basis values at the
+  // electrons [W][N][K] and at the points [2][W][S][K], ratio factors [W][S][N][2], the group
+  // tiles [groups][2][K][K][2] (all in the context dtype) and the group weight sums (double)
+  DevBuf d_rdm_rp, d_rdm_iq, d_rdm_pe, d_rdm_pp, d_rdm_f, d_rdm_tile, d_rdm_wsum;
   // [counted] energy components (aiqmc_energy_components, components.hip), per batch: the
   // all-electron E_L [B], an imaginary part [B], grad log|psi| [B][3N]
   DevBuf d_comp;

@@ -352,4 +352,21 @@ __device__ __forceinline__ void philox_normal3f(uint64_t seed, uint64_t step, ui
   out[2] = r1 * c1;
 }
 
+// psi' / psi = exp(dl) (cos dp + i sin dp) from the differences of log|psi| and of the phase
+// (aiqmc_spin_squared, aiqmc_rdm_accumulate)
+__device__ __forceinline__ void unit_ratio(float dl, float dp, float& re, float& im) {
+  float s, c;
+  sincosf(dp, &s, &c);
+  const float a = expf(dl);
+  re = a * c;
+  im = a * s;
+}
+__device__ __forceinline__ void unit_ratio(double dl, double dp, double& re, double& im) {
+  double s, c;
+  sincos(dp, &s, &c);
+  const double a = exp(dl);
+  re = a * c;
+  im = a * s;
+}
+
 }  // namespace aq

@@ -55,21 +55,6 @@ __global__ __launch_bounds__(256) void k_s2_exchange(const T* __restrict__ pos, 
   for (int c = 0; c < 3; ++c) xd[c] = xs[c];
 }
 
-__device__ __forceinline__ void unit_ratio(float dl, float dp, float& re, float& im) {
-  float s, c;
-  sincosf(dp, &s, &c);
-  const float a = expf(dl);
-  re = a * c;
-  im = a * s;
-}
-__device__ __forceinline__ void unit_ratio(double dl, double dp, double& re, double& im) {
-  double s, c;
-  sincos(dp, &s, &c);
-  const double a = exp(dl);
-  re = a * c;
-  im = a * s;
-}
-
 // lp / ph [nw][K + 1] of one chunk -> s2_re / s2_im [b0 + w], dlogabs / dphase [b0 + w][K] (optional)
 template <typename T, int G>
 __global__ __launch_bounds__(64) void k_s2_reduce(const T* __restrict__ lp, const T* __restrict__ ph, int K, int b0,

@@ -382,8 +382,8 @@ int aiqmc_energy_components(aiqmc_ctx* ctx, const void* pos, int32_t B, int32_t 
                             void* out /* [8][B], ctx dtype */, void* stream);
 
 /* Electron density and pair-correlation histograms, accumulated on the device across sweeps.
- * This is the DIAGONAL of the one-body density matrix (not ferminet/observables.py's
- * make_density_matrix, whose orbital projection needs an SCF basis): it needs only the walkers.
+ * This is the DIAGONAL of the one-body density matrix (the matrix itself on a Gaussian basis is
+ * aiqmc_rdm_accumulate): it needs only the walkers.
  * One call bins B walkers into the caller-owned device accumulator acc (int64 words, zeroed by
  * the caller before the first call, then only added to).  Three optional families; a family with
  * zero bins is absent together with its outside words:
@@ -434,6 +434,76 @@ int aiqmc_density_accumulate(aiqmc_ctx* ctx, const aiqmc_density_cfg* cfg, const
 /* Diagnostics: configurations per value launch of aiqmc_spin_squared (default 4096; nconf <= 0
  * restores it).  A chunk holds whole walkers, at least one.  Results do not depend on it. */
 int aiqmc_debug_set_obs_chunk(aiqmc_ctx* ctx, int32_t nconf);
+
+/* One-body reduced density matrix in a caller-supplied Gaussian basis (the quantity of
+ * ferminet/observables.py make_density_matrix; the basis is the caller's instead of an SCF run's).
+ * For each spin channel s (0 = the up slots, 1 = the down slots of the context's spin tables),
+ * functions phi_1..phi_K, walkers x_b ~ |psi|^2 with weights w_b and S points r'_bs per walker
+ * drawn from a known density q,
+ *   rho^s_ij = 1/(W S) sum_b w_b sum_s' sum_{e in s} phi_i(r_e) phi_j(r'_bs') psi(x_b; r_e -> r'_bs') / psi(x_b) / q(r'_bs'),
+ * W = sum_b w_b, summed over EVERY electron of the channel (this ansatz is not antisymmetric under
+ * same-spin exchange, so the first electron alone would not give its density matrix).  psi is
+ * complex, so rho is.
+ *
+ * Basis (aiqmc_set_rdm_basis; NULL clears it): contracted Cartesian Gaussian shells with l in
+ * {0, 1, 2}, each with its own centre, functions in the order 1 | x y z | xx xy xz yy yz zz; a
+ * function's value is x^a y^b z^c sum_p coefs[p] exp(-exps[p] r^2), coefficients as given (no
+ * norm is folded in).  mo_coeff (optional, [2][nao][norb] row-major, spin-major) makes
+ * phi^s_j = sum_a ao_a C[s][a][j]; NULL: the functions themselves (norb is ignored and is nao).
+ * q is a mixture of nq <= AIQMC_RDM_MAX_Q isotropic Gaussians,
+ *   q(r) = sum_k q_prob[k] (2 pi q_sigma[k]^2)^-3/2 exp(-|r - q_center[k]|^2 / (2 q_sigma[k]^2)),
+ * q_prob > 0 summing to 1 within 1e-12, q_sigma > 0.  phi_j / q stays bounded iff
+ * q_sigma^2 >= 1 / (2 alpha_min) for the smallest exponent of the basis.  AIQMC_EINVAL with a
+ * message naming the field: l > 2, nao > AIQMC_RDM_MAX_AO, norb > AIQMC_RDM_MAX_ORB, more than
+ * AIQMC_RDM_MAX_PRIM primitives, a shell without primitives, nq outside [1, AIQMC_RDM_MAX_Q], a
+ * bad q_prob / q_sigma, a null table.  The context keeps device copies; the call synchronises.
+ *
+ * aiqmc_rdm_accumulate: acc (device fp64, 1 + 2 K K 2 entries, K = norb) receives SUMS, not means:
+ * acc[0] = W and acc[1 + ((s K + i) K + j) 2 + {0, 1}] = Re, Im of W S rho^s_ij; accumulate != 0
+ * adds into acc instead of overwriting it.  rng_mode AIQMC_RNG_HOST: rprime_in [B][S][3] (ctx
+ * dtype) are the points; AIQMC_RNG_PHILOX: point (b, s) is drawn from q with stream id b S + s of
+ * (seed, step): kind 25's first uniform u picks the smallest k with u < q_prob[0] + .. + q_prob[k]
+ * (partial sums in fp64; the last component takes what is left), kind 24's three normals g give
+ * r' = fma(sigma_k, g, c_k) in the ctx dtype.  weights: [B] ctx dtype or NULL (all 1).  Optional
+ * outputs: rprime_out [B][S][3], ratio_out [B][S][N][2] = (log|psi|, phase) at the walker with
+ * electron slot e at r'_bs minus those at the walker -- bit for bit differences of aiqmc_logpsi
+ * values, the moved configurations go through its launch.  Cost: N S + 1 value forwards per
+ * walker in chunks of the aiqmc_debug_set_obs_chunk size (a chunk is a whole number of groups of
+ * AIQMC_RDM_GROUP walkers, or the whole batch).  Summation order, a function of (B, S, K) and the
+ * channel sizes only: rows (walker, point, electron of the channel) ascending within a group of
+ * AIQMC_RDM_GROUP walkers (by index within the call) in the ctx dtype on the matrix cores
+ * (v_mfma_{f32,f64}_16x16x4), the group tiles added into acc in fp64, groups ascending; no
+ * atomics, the same bits run to run and for any chunking.  The Gaussians and q are evaluated in
+ * fp64 for both dtypes and rounded once.  Nothing is clamped.  B == 0 returns AIQMC_OK and writes
+ * nothing.  AIQMC_ESTATE without parameters or without a basis; AIQMC_EINVAL for S < 1, an
+ * unknown rng_mode, AIQMC_RNG_HOST with a null rprime_in, a null acc.
+ *
+ * aiqmc_rdm_basis_values: out[M][K] (ctx dtype) = phi^spin_j(points[m]) for points [M][3] (ctx
+ * dtype), the basis evaluator alone.  Needs the basis, not the parameters. */
+#define AIQMC_RDM_GROUP 32
+#define AIQMC_RDM_MAX_AO 128
+#define AIQMC_RDM_MAX_ORB 64
+#define AIQMC_RDM_MAX_PRIM 512
+#define AIQMC_RDM_MAX_Q 16
+typedef struct aiqmc_rdm_basis {
+  int32_t nshell;
+  const int32_t* shell_l;       /* [nshell] */
+  const int32_t* shell_nprim;   /* [nshell] */
+  const double* shell_center;   /* [nshell][3] */
+  const double* exps;           /* [sum shell_nprim], shell after shell */
+  const double* coefs;          /* the same layout */
+  int32_t norb;
+  const double* mo_coeff;       /* [2][nao][norb] or NULL */
+  int32_t nq;
+  const double* q_center;       /* [nq][3] */
+  const double* q_sigma;        /* [nq] */
+  const double* q_prob;         /* [nq] */
+} aiqmc_rdm_basis;
+int aiqmc_set_rdm_basis(aiqmc_ctx* ctx, const aiqmc_rdm_basis* basis);
+int aiqmc_rdm_accumulate(aiqmc_ctx* ctx, const void* pos, int32_t B, int32_t S, int32_t rng_mode,
+                         const void* rprime_in, uint64_t seed, uint64_t step, const void* weights, double* acc,
+                         int32_t accumulate, void* rprime_out, void* ratio_out, void* stream);
+int aiqmc_rdm_basis_values(aiqmc_ctx* ctx, const void* points, int32_t M, int32_t spin, void* out, void* stream);
 
 /* Space-warp transform between nuclear geometries with its Jacobian (correlated sampling: the
  * walkers of one run at the context's atoms R evaluated at M nearby geometries R'_m).  The warp is

@@ -8,6 +8,7 @@ satisfies the library's NEEDED entry by SONAME).
 from __future__ import annotations
 
 import collections
+import contextlib
 import ctypes
 import functools
 import os
@@ -289,6 +290,24 @@ def _stream(device) -> ctypes.c_void_p:
     return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
+def _call(name: str, *args, device=None, stream: bool = True, raw: bool = False):
+    """The one call path into the library: symbol `name` with args (a tensor or None goes through
+    _ptr, anything else as it is; _SIGNATURES converts Python numbers), then the current stream of
+    `device` (default: the first tensor argument's) when `stream` is set, with that device current
+    for the call and the caller's restored after it.  check()s the return code; raw: returns the
+    library's return value unchecked instead."""
+    if device is None:
+        device = next(a.device for a in args if isinstance(a, torch.Tensor))
+    args = [_ptr(a) if a is None or isinstance(a, torch.Tensor) else a for a in args]
+    if stream:
+        args.append(_stream(device))
+    with torch.cuda.device(device):
+        rc = getattr(load(), name)(*args)
+    if not raw:
+        check(rc, name)
+    return rc
+
+
 def energy_stats(e_l: torch.Tensor, finalize: bool = True) -> torch.Tensor:
     """aiqmc_energy_stats on a device tensor of local energies (float32/float64): a float64 device
     tensor [sum |e - m|^2, n m, n m^2, n, mean, variance] (the last two only with finalize)."""
@@ -296,8 +315,7 @@ def energy_stats(e_l: torch.Tensor, finalize: bool = True) -> torch.Tensor:
         raise ValueError("energy_stats: a float32/float64 device tensor is required")
     e = e_l.contiguous().reshape(-1)
     out = torch.empty(6, dtype=torch.float64, device=e.device)
-    check(load().aiqmc_energy_stats(_ptr(e), _dt(e), e.numel(), _ptr(out), 1 if finalize else 0, _stream(e.device)),
-          "aiqmc_energy_stats")
+    _call("aiqmc_energy_stats", e, _dt(e), e.numel(), out, 1 if finalize else 0)
     return out
 
 
@@ -318,9 +336,8 @@ def loss_weights(e_l: torch.Tensor, clip_scale: float, center_at_clipped: bool, 
     cr = torch.empty_like(er)
     ci = torch.empty_like(er) if cplx else None
     st = torch.empty(5, dtype=torch.float64, device=er.device)
-    check(load().aiqmc_loss_weights(_ptr(er), _ptr(ei), _dt(er), n, float(clip_scale), 1 if center_at_clipped else 0,
-                                    float(wscale), _ptr(wr), _ptr(wi), _ptr(cr), _ptr(ci), _ptr(st),
-                                    _stream(er.device)), "aiqmc_loss_weights")
+    _call("aiqmc_loss_weights", er, ei, _dt(er), n, float(clip_scale), 1 if center_at_clipped else 0, float(wscale),
+          wr, wi, cr, ci, st)
     clipped = torch.complex(cr, ci) if cplx else cr
     return wr, wi, clipped.reshape(e_l.shape), st
 
@@ -332,21 +349,17 @@ def loss_level(level: int, er: torch.Tensor, ei: Optional[torch.Tensor], L1=None
     clipped_re, clipped_im or None, head [2] float64 = sums of the clipped energies)."""
     n = er.numel()
     dev = er.device
-    lib = load()
-    st = _stream(dev)
     if level in (1, 2):
         out = torch.empty(6 if level == 1 else 2, dtype=torch.float64, device=dev)
-        check(lib.aiqmc_loss_level(level, _ptr(er), _ptr(ei), _dt(er), n, _ptr(L1), None, 0.0, 0.0, 0, None, None,
-                                   None, None, _ptr(out), st), "aiqmc_loss_level")
+        _call("aiqmc_loss_level", level, er, ei, _dt(er), n, L1, None, 0.0, 0.0, 0, None, None, None, None, out)
         return out
     w = torch.empty(2 if g0 else 1, n, dtype=er.dtype, device=dev)
     wp = torch.empty_like(er) if want_phase else None
     cr = torch.empty_like(er)
     ci = torch.empty_like(er) if ei is not None else None
     head = torch.empty(2, dtype=torch.float64, device=dev)
-    check(lib.aiqmc_loss_level(3, _ptr(er), _ptr(ei), _dt(er), n, _ptr(L1), _ptr(L2), float(clip_scale),
-                               float(wscale), 1 if g0 else 0, _ptr(w), _ptr(wp), _ptr(cr), _ptr(ci), _ptr(head), st),
-          "aiqmc_loss_level")
+    _call("aiqmc_loss_level", 3, er, ei, _dt(er), n, L1, L2, float(clip_scale), float(wscale), 1 if g0 else 0,
+          w, wp, cr, ci, head)
     return w, wp, cr, ci, head
 
 
@@ -355,8 +368,7 @@ def loss_pack(g: torch.Tensor, gp: Optional[torch.Tensor], g0: Optional[torch.Te
     P = g.numel()
     L3 = torch.empty(2 + P * (2 if g0 is not None else 1), dtype=torch.float64, device=g.device)
     L3[:2].copy_(head)
-    check(load().aiqmc_loss_pack(_ptr(g), _ptr(gp), _ptr(g0), _dt(g), P, _ptr(L3), _stream(g.device)),
-          "aiqmc_loss_pack")
+    _call("aiqmc_loss_pack", g, gp, g0, _dt(g), P, L3)
     return L3
 
 
@@ -365,8 +377,8 @@ def loss_final(L1: torch.Tensor, L3: torch.Tensor, P: int, g0: bool, center_at_c
     """(grad [P] of dtype, stats [6] float64) from the summed level vectors."""
     grad = torch.empty(P, dtype=dtype, device=L1.device)
     stats = torch.empty(6, dtype=torch.float64, device=L1.device)
-    check(load().aiqmc_loss_final(_ptr(L1), _ptr(L3), P, 1 if g0 else 0, 1 if center_at_clipped else 0, int(world),
-                                  _dt(dtype), _ptr(grad), _ptr(stats), _stream(L1.device)), "aiqmc_loss_final")
+    _call("aiqmc_loss_final", L1, L3, P, 1 if g0 else 0, 1 if center_at_clipped else 0, int(world), _dt(dtype), grad,
+          stats)
     return grad, stats
 
 
@@ -403,9 +415,7 @@ def sr_gram(o_re: torch.Tensor, o_im: Optional[torch.Tensor] = None, center_re: 
     elif not (out.is_cuda and out.device == dev and out.dtype == torch.float64 and out.is_contiguous()
               and out.numel() == n_out):
         raise ValueError(f"sr_gram: out must be a contiguous float64 device vector of {n_out} entries")
-    with torch.cuda.device(dev):
-        check(load().aiqmc_sr_gram(_ptr(a), _ptr(b), _dt(a), B, P, _ptr(cr), _ptr(ci), _ptr(out),
-                                   1 if accumulate else 0, _stream(dev)), "aiqmc_sr_gram")
+    _call("aiqmc_sr_gram", a, b, _dt(a), B, P, cr, ci, out, 1 if accumulate else 0)
     return out
 
 
@@ -442,9 +452,7 @@ def corr_level(level: int, logabs0: torch.Tensor, e0: Optional[torch.Tensor], lo
         out = torch.empty((M,) if level == 1 else (M, 5 if level == 2 else 2), dtype=torch.float64, device=dev)
         l1 = None if L1 is None else L1.to(dev, torch.float64).contiguous()
         l2 = None if L2 is None else L2.to(dev, torch.float64).contiguous()
-        with torch.cuda.device(dev):
-            check(load().aiqmc_corr_level(level, _dt(a1), n, M, _ptr(a0), _ptr(x0), _ptr(a1), _ptr(lj), _ptr(x1),
-                                          _ptr(l1), _ptr(l2), _ptr(out), _stream(dev)), "aiqmc_corr_level")
+        _call("aiqmc_corr_level", level, _dt(a1), n, M, a0, x0, a1, lj, x1, l1, l2, out)
         return out
     lw = 2.0 * (a1.double() - a0.double()[None]) + lj.double()
     if level == 1:
@@ -467,8 +475,7 @@ def corr_final(L2: torch.Tensor, L3: torch.Tensor) -> torch.Tensor:
     if L2.is_cuda:
         l2, l3 = L2.to(torch.float64).contiguous(), L3.to(L2.device, torch.float64).contiguous()
         res = torch.empty(M, 5, dtype=torch.float64, device=L2.device)
-        with torch.cuda.device(L2.device):
-            check(load().aiqmc_corr_final(_ptr(l2), _ptr(l3), M, _ptr(res), _stream(L2.device)), "aiqmc_corr_final")
+        _call("aiqmc_corr_final", l2, l3, M, res)
         return res
     l2, l3 = L2.double().reshape(M, 5), L3.double().reshape(M, 2)
     n, sd, sd2 = l2[:, 0], l3[:, 0], l3[:, 1]
@@ -501,19 +508,23 @@ def blocking_update(x: torch.Tensor, L: int, acc: torch.Tensor, pend: torch.Tens
     for t, n, what in zip((acc, pend, scratch), _blocking_words(B, K, int(L)), ("acc", "pend", "scratch")):
         if not (t.dtype == torch.float64 and t.device == x.device and t.is_contiguous() and t.numel() == n):
             raise ValueError(f"blocking_update: {what} must be a contiguous float64 tensor of {n} words on {x.device}")
-    with torch.cuda.device(x.device):
-        check(load().aiqmc_blocking_update(_ptr(x), _dt(x), B, K, int(L), _ptr(acc), _ptr(pend), _ptr(scratch),
-                                           _stream(x.device)), "aiqmc_blocking_update")
+    _call("aiqmc_blocking_update", x, _dt(x), B, K, int(L), acc, pend, scratch)
 
 
 def energy_stats_final(out: torch.Tensor) -> torch.Tensor:
     """aiqmc_energy_stats_final: out[4..5] = [mean, variance] from a summed out[0..3], in place."""
-    check(load().aiqmc_energy_stats_final(_ptr(out), _stream(out.device)), "aiqmc_energy_stats_final")
+    _call("aiqmc_energy_stats_final", out)
     return out
 
 
 class Context:
-    """One aiqmc_ctx: a system/network configuration bound to one GPU and dtype."""
+    """One aiqmc_ctx: a system/network configuration bound to one GPU and dtype.
+
+    Every method reaches the library through _call, which makes the context's device current for
+    the call and restores the caller's afterwards: after any Context call the current torch device
+    is what it was before it.  A method stages its inputs with the vocabulary below (_pos, _inplace,
+    _dev, _grad_arg, _rng, _weights, _acc, _obs_chunk), allocates its outputs with _new and makes
+    one _call; it adds nothing else."""
 
     def __init__(self, nelectrons: int, natoms: int, nspins: Sequence[int], atoms, charges,
                  spin_up_indices, spin_down_indices, parallel_indices, antiparallel_indices,
@@ -560,11 +571,10 @@ class Context:
             cfg.hidden_dims[l][1] = 4
             cfg.hidden_dims_ynlm[l] = 6
         h = ctypes.c_void_p()
-        with torch.cuda.device(self.device):
-            check(lib.aiqmc_create(ctypes.byref(cfg), ctypes.byref(h)), "aiqmc_create")
+        _call("aiqmc_create", ctypes.byref(cfg), ctypes.byref(h), device=self.device, stream=False)
         self._h = h
         self._lib = lib
-        self.nparams = int(lib.aiqmc_param_count(h))
+        self.nparams = int(self._call("aiqmc_param_count", stream=False, raw=True))
 
     @classmethod
     def for_system(cls, system, dtype: torch.dtype = torch.float32, device: int = 0, atoms=None) -> "Context":
@@ -584,22 +594,16 @@ class Context:
                 pass
             self._h = None
 
-    # -- kernel timing (HIP events on the launch stream) -------------------
-    def profile(self, on: bool = True):
-        check(self._lib.aiqmc_profile_enable(self._h, 1 if on else 0), "aiqmc_profile_enable")
+    # -- the call path -----------------------------------------------------
+    def _call(self, name: str, *args, stream: bool = True, raw: bool = False):
+        """The module's _call on this context: the handle first, on the context's device."""
+        return _call(name, self._h, *args, device=self.device, stream=stream, raw=raw)
 
-    def profile_read(self, slot: int):
-        """(summed kernel ms, launches) recorded in `slot` since the last read."""
-        ms = ctypes.c_double()
-        n = ctypes.c_int64()
-        check(self._lib.aiqmc_profile_read(self._h, int(slot), ctypes.byref(ms), ctypes.byref(n)),
-              "aiqmc_profile_read")
-        return ms.value, n.value
+    # -- the argument vocabulary -------------------------------------------
+    def _new(self, *shape, dtype=None) -> torch.Tensor:
+        """An output: an uninitialised tensor on the context's device, in its dtype by default."""
+        return torch.empty(*shape, dtype=dtype or self.dtype, device=self.device)
 
-    def workspace_bytes(self) -> int:
-        return int(self._lib.aiqmc_workspace_bytes(self._h))
-
-    # -- helpers ---------------------------------------------------------
     def _pos(self, pos: torch.Tensor) -> torch.Tensor:
         if not isinstance(pos, torch.Tensor):
             pos = torch.as_tensor(np.asarray(pos))
@@ -614,22 +618,91 @@ class Context:
             raise ValueError(f"{who} needs a contiguous device tensor of the context dtype{note}")
         return pos.numel() // (3 * self.N)
 
-    def _rot(self, rot: Optional[torch.Tensor], B: int) -> Optional[torch.Tensor]:
-        """Injected grid rotations [B,3,3] in the context's dtype on its device (None: Philox)."""
-        if rot is None:
+    def _dev(self, t, n: Optional[int], what: Optional[str] = None, real: bool = False) -> torch.Tensor:
+        """An input, converted: t as a contiguous tensor of the context's dtype on its device, of n
+        values when n is given (what: its name in the error); real: a complex t gives its real part."""
+        t = torch.as_tensor(t)
+        if real and torch.is_complex(t):
+            t = t.real
+        t = t.to(self.device, self.dtype).contiguous()
+        if n is not None and t.numel() != n:
+            raise ValueError(f"{what}: expected {n} values, got {t.numel()}" if what else
+                             f"expected {n} values, got {t.numel()}")
+        return t
+
+    def _grad_arg(self, g: torch.Tensor, B: int, what: str) -> torch.Tensor:
+        """An input that is refused instead of converted (apart from _dev for that reason alone): a
+        gradient [B, 3N] that an earlier call returned is already a device tensor of the context
+        dtype, and anything else is a mistake that a conversion would hide."""
+        if not (isinstance(g, torch.Tensor) and g.is_cuda and g.dtype == self.dtype):
+            raise ValueError(f"{what} must be a device tensor of the context dtype {self.dtype}")
+        if g.numel() != B * 3 * self.N:
+            raise ValueError(f"{what}: expected {B * 3 * self.N} values, got {g.numel()}")
+        return g.contiguous()
+
+    def _rng(self, what: str, **draws):
+        """The draws of a sampling call, name=(tensor or None, values expected): (rng mode, staged
+        draws in the given order).  All None: Philox, (None, ...); all given: host mode, each
+        through _dev; anything between is refused."""
+        given = [k for k, (t, _) in draws.items() if t is not None]
+        if given and len(given) != len(draws):
+            names = list(draws)
+            raise ValueError(f"{', '.join(names[:-1])} and {names[-1]} are injected together or not at all")
+        mode = AIQMC_RNG_HOST if given else AIQMC_RNG_PHILOX
+        return mode, tuple(self._dev(t, n, f"{what}: {k}") if given else None for k, (t, n) in draws.items())
+
+    def _weights(self, weights, B: int) -> Optional[torch.Tensor]:
+        """Per-walker weights [B] in the context's dtype on its device, or None."""
+        if weights is None:
             return None
-        r = rot.to(self.device, self.dtype).contiguous()
-        if r.numel() != 9 * B:
-            raise ValueError("rot must be [B,3,3]")
-        return r
+        w = torch.as_tensor(weights).to(self.device, self.dtype).contiguous().reshape(-1)
+        if w.numel() != B:
+            raise ValueError("weights must have one entry per walker")
+        return w
+
+    def _acc(self, acc, n: int, dtype: torch.dtype, who: str) -> torch.Tensor:
+        """A caller-owned accumulator, written in place: never converted, so it is refused unless it
+        is contiguous, of dtype, on the context's device and n words long."""
+        if not (isinstance(acc, torch.Tensor) and acc.dtype == dtype and acc.device == self.device
+                and acc.is_contiguous() and acc.numel() == n):
+            raise ValueError(f"{who}: acc must be a contiguous {str(dtype).replace('torch.', '')} tensor of {n} "
+                             f"words on {self.device}")
+        return acc
+
+    @contextlib.contextmanager
+    def _obs_chunk(self, chunk: Optional[int]):
+        """The configurations per value launch of the observables (spin_squared, rdm_accumulate) set
+        to chunk inside the block and back to the default after it; None: left alone."""
+        if chunk is None:
+            yield
+            return
+        if int(chunk) <= 0:
+            raise ValueError("chunk must be positive")
+        self._call("aiqmc_debug_set_obs_chunk", int(chunk), stream=False)
+        try:
+            yield
+        finally:
+            self._call("aiqmc_debug_set_obs_chunk", 0, stream=False)
+
+    # -- kernel timing (HIP events on the launch stream) -------------------
+    def profile(self, on: bool = True):
+        self._call("aiqmc_profile_enable", 1 if on else 0, stream=False)
+
+    def profile_read(self, slot: int):
+        """(summed kernel ms, launches) recorded in `slot` since the last read."""
+        ms = ctypes.c_double()
+        n = ctypes.c_int64()
+        self._call("aiqmc_profile_read", int(slot), ctypes.byref(ms), ctypes.byref(n), stream=False)
+        return ms.value, n.value
+
+    def workspace_bytes(self) -> int:
+        return int(self._call("aiqmc_workspace_bytes", stream=False, raw=True))
 
     def set_params(self, flat: np.ndarray):
         flat = np.ascontiguousarray(np.asarray(flat, dtype=np.float64).reshape(-1))
         if flat.size != self.nparams:
             raise ValueError(f"expected {self.nparams} parameters, got {flat.size}")
-        with torch.cuda.device(self.device):
-            check(self._lib.aiqmc_set_params(self._h, flat.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
-                                             flat.size, _stream(self.device)), "aiqmc_set_params")
+        self._call("aiqmc_set_params", flat.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), flat.size)
 
     def set_params_device(self, flat: torch.Tensor):
         """Canonical parameters already on this context's device (float64, tree_flatten order):
@@ -639,27 +712,23 @@ class Context:
             raise ValueError("set_params_device needs a contiguous float64 tensor on the context's device")
         if flat.numel() != self.nparams:
             raise ValueError(f"expected {self.nparams} parameters, got {flat.numel()}")
-        with torch.cuda.device(self.device):
-            check(self._lib.aiqmc_set_params_device(self._h, _ptr(flat), flat.numel(), _stream(self.device)),
-                  "aiqmc_set_params_device")
+        self._call("aiqmc_set_params_device", flat, flat.numel())
         self._flat_keep = flat   # the repack reads it later on the stream: keep it alive until then
 
     def logpsi(self, pos: torch.Tensor, with_phase: bool = True):
         p = self._pos(pos)
         B = p.shape[0]
-        logabs = torch.empty(B, dtype=self.dtype, device=self.device)
-        phase = torch.empty(B, dtype=self.dtype, device=self.device) if with_phase else None
-        check(self._lib.aiqmc_logpsi(self._h, _ptr(p), B, _ptr(logabs), _ptr(phase), _stream(self.device)),
-              "aiqmc_logpsi")
+        logabs = self._new(B)
+        phase = self._new(B) if with_phase else None
+        self._call("aiqmc_logpsi", p, B, logabs, phase)
         return logabs, phase
 
     def orbitals(self, pos: torch.Tensor):
         """The complex orbital matrix [B, N, N] (make_orbitals.apply, nn.py:409-506)."""
         p = self._pos(pos)
         B = p.shape[0]
-        out = torch.empty(B, self.N, self.N, 2, dtype=self.dtype, device=self.device)
-        check(self._lib.aiqmc_orbitals(self._h, _ptr(p), B, _ptr(out), None, None, _stream(self.device)),
-              "aiqmc_orbitals")
+        out = self._new(B, self.N, self.N, 2)
+        self._call("aiqmc_orbitals", p, B, out, None, None)
         return torch.view_as_complex(out)
 
     # -- observables (aiqmc/observables.py) ---------------------------------
@@ -672,22 +741,11 @@ class Context:
         walkers, at least one); the result does not depend on it."""
         p = self._pos(pos)
         B = p.shape[0]
-        nup, ndn = self.nspins
-        re = torch.empty(B, dtype=self.dtype, device=self.device)
-        im = torch.empty(B, dtype=self.dtype, device=self.device)
-        dl = torch.empty(B, nup, ndn, dtype=self.dtype, device=self.device) if want_pairs else None
-        dp = torch.empty(B, nup, ndn, dtype=self.dtype, device=self.device) if want_pairs else None
-        if chunk is not None:
-            if int(chunk) <= 0:
-                raise ValueError("chunk must be positive")
-            check(self._lib.aiqmc_debug_set_obs_chunk(self._h, int(chunk)), "aiqmc_debug_set_obs_chunk")
-        try:
-            with torch.cuda.device(self.device):
-                check(self._lib.aiqmc_spin_squared(self._h, _ptr(p), B, _ptr(re), _ptr(im), _ptr(dl), _ptr(dp),
-                                                   _stream(self.device)), "aiqmc_spin_squared")
-        finally:
-            if chunk is not None:
-                self._lib.aiqmc_debug_set_obs_chunk(self._h, 0)
+        re, im = self._new(B), self._new(B)
+        dl = self._new(B, *self.nspins) if want_pairs else None
+        dp = self._new(B, *self.nspins) if want_pairs else None
+        with self._obs_chunk(chunk):
+            self._call("aiqmc_spin_squared", p, B, re, im, dl, dp)
         s2 = torch.complex(re, im)
         return (s2, dl, dp) if want_pairs else s2
 
@@ -696,9 +754,8 @@ class Context:
         context charges, Z_eff under an ECP)."""
         p = self._pos(pos)
         B = p.shape[0]
-        mu = torch.empty(B, 3, dtype=self.dtype, device=self.device)
-        with torch.cuda.device(self.device):
-            check(self._lib.aiqmc_dipole(self._h, _ptr(p), B, _ptr(mu), _stream(self.device)), "aiqmc_dipole")
+        mu = self._new(B, 3)
+        self._call("aiqmc_dipole", p, B, mu)
         return mu
 
     def energy_components(self, pos: torch.Tensor, complex_output: bool = False, rot: Optional[torch.Tensor] = None,
@@ -710,13 +767,9 @@ class Context:
         accumulator (aiqmc/Energy/components.py)."""
         p = self._pos(pos)
         B = p.shape[0]
-        out = torch.empty(len(COMPONENT_NAMES), B, dtype=self.dtype, device=self.device)
-        r = self._rot(rot, B)
-        mode = AIQMC_RNG_HOST if r is not None else AIQMC_RNG_PHILOX
-        with torch.cuda.device(self.device):
-            check(self._lib.aiqmc_energy_components(self._h, _ptr(p), B, 1 if complex_output else 0, mode, _ptr(r),
-                                                    ctypes.c_uint64(seed), ctypes.c_uint64(offset), _ptr(out),
-                                                    _stream(self.device)), "aiqmc_energy_components")
+        out = self._new(len(COMPONENT_NAMES), B)
+        mode, (r,) = self._rng("energy_components", rot=(rot, 9 * B))
+        self._call("aiqmc_energy_components", p, B, 1 if complex_output else 0, mode, r, seed, offset, out)
         return out
 
     def density_layout(self, cfg: AiqmcDensityCfg) -> dict:
@@ -725,8 +778,7 @@ class Context:
         names in DENSITY_FIELDS order.  privatised: radial + pair take the LDS path."""
         off = (ctypes.c_int64 * 8)()
         nw, priv = ctypes.c_int64(0), ctypes.c_int32(0)
-        check(self._lib.aiqmc_density_layout(self._h, ctypes.byref(cfg), off, ctypes.byref(nw), ctypes.byref(priv)),
-              "aiqmc_density_layout")
+        self._call("aiqmc_density_layout", ctypes.byref(cfg), off, ctypes.byref(nw), ctypes.byref(priv), stream=False)
         ends = list(off[1:]) + [nw.value]
         return {"offsets": dict(zip(DENSITY_FIELDS, off)),
                 "sizes": {k: e - o for k, o, e in zip(DENSITY_FIELDS, off, ends)},
@@ -739,19 +791,8 @@ class Context:
         (zeroed by the caller before the first call), in place on the current stream."""
         p = self._pos(pos)
         B = p.shape[0]
-        n_words = self.density_layout(cfg)["n_words"]
-        if not (isinstance(acc, torch.Tensor) and acc.dtype == torch.int64 and acc.device == self.device
-                and acc.is_contiguous() and acc.numel() == n_words):
-            raise ValueError(f"density_accumulate: acc must be a contiguous int64 tensor of {n_words} words on "
-                             f"{self.device}")
-        w = None
-        if weights is not None:
-            w = torch.as_tensor(weights).to(self.device, self.dtype).contiguous().reshape(-1)
-            if w.numel() != B:
-                raise ValueError("weights must have one entry per walker")
-        with torch.cuda.device(self.device):
-            check(self._lib.aiqmc_density_accumulate(self._h, ctypes.byref(cfg), _ptr(p), B, _ptr(w), _ptr(acc),
-                                                     _stream(self.device)), "aiqmc_density_accumulate")
+        acc = self._acc(acc, self.density_layout(cfg)["n_words"], torch.int64, "density_accumulate")
+        self._call("aiqmc_density_accumulate", ctypes.byref(cfg), p, B, self._weights(weights, B), acc)
         return acc
 
     # -- one-body density matrix (aiqmc/observables.py make_density_matrix) ------
@@ -789,24 +830,20 @@ class Context:
             b.norb = nao
         b.nq, b.q_center, b.q_sigma, b.q_prob = qs.size, pd(qc), pd(qs), pd(qp)
         self._rdm_token = None
-        with torch.cuda.device(self.device):
-            check(self._lib.aiqmc_set_rdm_basis(self._h, ctypes.byref(b)), "aiqmc_set_rdm_basis")
+        self._call("aiqmc_set_rdm_basis", ctypes.byref(b), stream=False)
         self._rdm_token, self.rdm_norb = token, int(b.norb)
 
     def clear_rdm_basis(self) -> None:
         self._rdm_token = None
-        check(self._lib.aiqmc_set_rdm_basis(self._h, None), "aiqmc_set_rdm_basis")
+        self._call("aiqmc_set_rdm_basis", None, stream=False)
 
     def rdm_basis_values(self, points: torch.Tensor, spin: int = 0) -> torch.Tensor:
         """aiqmc_rdm_basis_values: the basis functions (MO-contracted with spin's coefficients when
         set) at points [M, 3] -> [M, norb] of the context dtype."""
-        p = torch.as_tensor(points).to(self.device, self.dtype).contiguous().reshape(-1, 3)
+        p = self._dev(points, None).reshape(-1, 3)
         M = p.shape[0]
-        K = int(getattr(self, "rdm_norb", 0))
-        out = torch.empty(M, K, dtype=self.dtype, device=self.device)
-        with torch.cuda.device(self.device):
-            check(self._lib.aiqmc_rdm_basis_values(self._h, _ptr(p), M, int(spin), _ptr(out), _stream(self.device)),
-                  "aiqmc_rdm_basis_values")
+        out = self._new(M, int(getattr(self, "rdm_norb", 0)))
+        self._call("aiqmc_rdm_basis_values", p, M, int(spin), out)
         return out
 
     def rdm_accumulate(self, pos: torch.Tensor, samples: int, rprime: Optional[torch.Tensor] = None, seed: int = 0,
@@ -824,34 +861,14 @@ class Context:
         n = 1 + 4 * K * K
         if acc is None:
             acc = torch.zeros(n, dtype=torch.float64, device=self.device)
-        elif not (isinstance(acc, torch.Tensor) and acc.dtype == torch.float64 and acc.device == self.device
-                  and acc.is_contiguous() and acc.numel() == n):
-            raise ValueError(f"rdm_accumulate: acc must be a contiguous float64 tensor of {n} entries on {self.device}")
-        r = None
-        if rprime is not None:
-            r = torch.as_tensor(rprime).to(self.device, self.dtype).contiguous()
-            if r.numel() != B * max(S, 0) * 3:
-                raise ValueError("rprime must be [B, S, 3]")
-        w = None
-        if weights is not None:
-            w = torch.as_tensor(weights).to(self.device, self.dtype).contiguous().reshape(-1)
-            if w.numel() != B:
-                raise ValueError("weights must have one entry per walker")
-        rp = torch.empty(B, max(S, 0), 3, dtype=self.dtype, device=self.device) if want_points else None
-        ro = torch.empty(B, max(S, 0), self.N, 2, dtype=self.dtype, device=self.device) if want_ratios else None
-        if chunk is not None:
-            if int(chunk) <= 0:
-                raise ValueError("chunk must be positive")
-            check(self._lib.aiqmc_debug_set_obs_chunk(self._h, int(chunk)), "aiqmc_debug_set_obs_chunk")
-        try:
-            with torch.cuda.device(self.device):
-                check(self._lib.aiqmc_rdm_accumulate(
-                    self._h, _ptr(p), B, S, AIQMC_RNG_HOST if r is not None else AIQMC_RNG_PHILOX, _ptr(r),
-                    ctypes.c_uint64(seed), ctypes.c_uint64(step), _ptr(w), _ptr(acc), 1 if accumulate else 0, _ptr(rp),
-                    _ptr(ro), _stream(self.device)), "aiqmc_rdm_accumulate")
-        finally:
-            if chunk is not None:
-                self._lib.aiqmc_debug_set_obs_chunk(self._h, 0)
+        else:
+            self._acc(acc, n, torch.float64, "rdm_accumulate")
+        mode, (r,) = self._rng("rdm_accumulate", rprime=(rprime, B * max(S, 0) * 3))
+        w = self._weights(weights, B)
+        rp = self._new(B, max(S, 0), 3) if want_points else None
+        ro = self._new(B, max(S, 0), self.N, 2) if want_ratios else None
+        with self._obs_chunk(chunk):
+            self._call("aiqmc_rdm_accumulate", p, B, S, mode, r, seed, step, w, acc, 1 if accumulate else 0, rp, ro)
         out = (acc,) + ((rp,) if want_points else ()) + ((ro,) if want_ratios else ())
         return out if len(out) > 1 else acc
 
@@ -869,55 +886,47 @@ class Context:
         if na.dim() != 3 or tuple(na.shape[1:]) != (self.A, 3):
             raise ValueError(f"new_atoms must be [M, {self.A}, 3], got {tuple(na.shape)}")
         M = na.shape[0]
-        na = na.to(self.device).contiguous()
-        newpos = torch.empty(M, B, 3 * self.N, dtype=self.dtype, device=self.device)
-        logjac = torch.empty(M, B, dtype=self.dtype, device=self.device)
+        na = na.to(self.device).contiguous()   # float64 whatever the context's dtype: not _dev
+        newpos, logjac = self._new(M, B, 3 * self.N), self._new(M, B)
         if M and B:
-            with torch.cuda.device(self.device):
-                check(self._lib.aiqmc_space_warp(self._h, _ptr(p), B, _ptr(na), M, _ptr(newpos), _ptr(logjac),
-                                                 _stream(self.device)), "aiqmc_space_warp")
+            self._call("aiqmc_space_warp", p, B, na, M, newpos, logjac)
         return newpos, logjac
 
-    def logpsi_grad(self, pos: torch.Tensor):
+    def _logpsi_grad(self, name: str, pos: torch.Tensor):
         p = self._pos(pos)
         B = p.shape[0]
-        logabs = torch.empty(B, dtype=self.dtype, device=self.device)
-        grad = torch.empty_like(p)
-        check(self._lib.aiqmc_logpsi_grad(self._h, _ptr(p), B, _ptr(logabs), _ptr(grad), _stream(self.device)),
-              "aiqmc_logpsi_grad")
+        logabs, grad = self._new(B), torch.empty_like(p)
+        self._call(name, p, B, logabs, grad)
         return logabs, grad
+
+    def logpsi_grad(self, pos: torch.Tensor):
+        return self._logpsi_grad("aiqmc_logpsi_grad", pos)
 
     def logpsi_grad_forward_mode(self, pos: torch.Tensor):
         """Diagnostics: the same quantity through the forward-mode kernel (cross-check)."""
-        p = self._pos(pos)
-        B = p.shape[0]
-        logabs = torch.empty(B, dtype=self.dtype, device=self.device)
-        grad = torch.empty_like(p)
-        check(self._lib.aiqmc_debug_logpsi_grad_forward(self._h, _ptr(p), B, _ptr(logabs), _ptr(grad),
-                                                        _stream(self.device)), "aiqmc_debug_logpsi_grad_forward")
-        return logabs, grad
+        return self._logpsi_grad("aiqmc_debug_logpsi_grad_forward", pos)
 
     def set_lap_waves(self, waves: int):
         """Waves per walker of the local energy's first-derivative pass (0 = by batch size)."""
-        check(self._lib.aiqmc_debug_set_lap_waves(self._h, int(waves)), "aiqmc_debug_set_lap_waves")
+        self._call("aiqmc_debug_set_lap_waves", int(waves), stream=False)
 
     def set_fuse_accept(self, on: bool):
         """Diagnostics: fused (default) or separate per-sweep acceptance launch in mc_step."""
-        check(self._lib.aiqmc_debug_set_fuse_accept(self._h, int(bool(on))), "aiqmc_debug_set_fuse_accept")
+        self._call("aiqmc_debug_set_fuse_accept", int(bool(on)), stream=False)
 
     def set_walker_pivots(self, reuse: bool):
         """Diagnostics: walker launches after an mc_step's first sweep re-use the previous sweep's
         Gauss-Jordan pivot order (default) or run partial pivoting every sweep."""
-        check(self._lib.aiqmc_debug_set_walker_pivots(self._h, int(bool(reuse))), "aiqmc_debug_set_walker_pivots")
+        self._call("aiqmc_debug_set_walker_pivots", int(bool(reuse)), stream=False)
 
     def set_packed_walkers(self, on: bool):
         """Diagnostics: walker launches of N <= 8 several per wave (default) or one wave each."""
-        check(self._lib.aiqmc_debug_set_packed_walkers(self._h, int(bool(on))), "aiqmc_debug_set_packed_walkers")
+        self._call("aiqmc_debug_set_packed_walkers", int(bool(on)), stream=False)
 
     def set_quad_pivoted(self, on: bool):
         """Diagnostics: the N <= 8 ECP quadrature launch factors every configuration with partial
         pivoting (on) instead of the walker's recorded order with a per-configuration fallback."""
-        check(self._lib.aiqmc_debug_set_quad_pivoted(self._h, int(bool(on))), "aiqmc_debug_set_quad_pivoted")
+        self._call("aiqmc_debug_set_quad_pivoted", int(bool(on)), stream=False)
 
     def set_fuse_reduce(self, mode):
         """Diagnostics: fp32 mc_step limdrift sums fused into the walker / proposal launches as
@@ -925,7 +934,7 @@ class Context:
         0 never (reduction launches summing the same integers: the same bits), 3 never with the
         fp64 tree-sum launch (k_taueff).  True/False map to 2/0."""
         m = 2 if mode is True else (0 if mode is False else int(mode))
-        check(self._lib.aiqmc_debug_set_fuse_reduce(self._h, m), "aiqmc_debug_set_fuse_reduce")
+        self._call("aiqmc_debug_set_fuse_reduce", m, stream=False)
 
     def limdrift_factor(self, sumsq: torch.Tensor, tstep: float, mode: int) -> float:
         """Diagnostics: the fp32 limdrift factor of the per-configuration |grad|^2 values `sumsq`
@@ -935,24 +944,20 @@ class Context:
             raise TypeError("sumsq must be a 1-D float32 tensor on the context's device")
         x = sumsq.contiguous()
         out = ctypes.c_double(0.0)
-        check(self._lib.aiqmc_debug_limdrift_factor(self._h, _ptr(x), int(x.numel()), float(tstep), int(mode),
-                                                    ctypes.byref(out), _stream(self.device)),
-              "aiqmc_debug_limdrift_factor")
+        self._call("aiqmc_debug_limdrift_factor", x, int(x.numel()), float(tstep), int(mode), ctypes.byref(out))
         return out.value
 
     def set_ablate(self, mask: int):
         """Development builds (-DAQ_ABLATE) only: skip proposal phases to time them."""
-        check(self._lib.aiqmc_debug_set_ablate(self._h, int(mask)), "aiqmc_debug_set_ablate")
+        self._call("aiqmc_debug_set_ablate", int(mask), stream=False)
 
     def set_proposal_reuse(self, on: bool):
         """Diagnostics: proposals from the walker cache (default) or recomputed from scratch."""
-        check(self._lib.aiqmc_debug_set_proposal_reuse(self._h, 1 if on else 0), "aiqmc_debug_set_proposal_reuse")
+        self._call("aiqmc_debug_set_proposal_reuse", 1 if on else 0, stream=False)
 
     def _read_draws(self, which: int, shape) -> torch.Tensor:
-        out = torch.empty(shape, dtype=self.dtype, device=self.device)
-        with torch.cuda.device(self.device):
-            check(self._lib.aiqmc_debug_read_draws(self._h, int(which), _ptr(out), out.numel(), _stream(self.device)),
-                  "aiqmc_debug_read_draws")
+        out = self._new(shape)
+        self._call("aiqmc_debug_read_draws", int(which), out, out.numel())
         return out
 
     def last_draws(self, B: int):
@@ -969,21 +974,23 @@ class Context:
 
     def phase_cycles(self):
         """Diagnostics (AQ_PHASE_PROF builds): per-phase cycle sums [32], then cleared."""
-        import numpy as np
         out = np.zeros(32, dtype=np.uint64)
-        check(self._lib.aiqmc_debug_phase_cycles(self._h, out.ctypes.data), "aiqmc_debug_phase_cycles")
+        self._call("aiqmc_debug_phase_cycles", out.ctypes.data, stream=False)
         return out
+
+    def _local_energy(self, name: str, pos: torch.Tensor, want_logabs: bool, want_grad: bool,
+                      out: Optional[torch.Tensor] = None):
+        p = self._pos(pos)
+        B = p.shape[0]
+        el = out if out is not None else self._new(B)
+        logabs = self._new(B) if want_logabs else None
+        grad = torch.empty_like(p) if want_grad else None
+        self._call(name, p, B, el, logabs, grad)
+        return el, logabs, grad
 
     def local_energy(self, pos: torch.Tensor, want_logabs: bool = False, want_grad: bool = False,
                      out: Optional[torch.Tensor] = None):
-        p = self._pos(pos)
-        B = p.shape[0]
-        el = out if out is not None else torch.empty(B, dtype=self.dtype, device=self.device)
-        logabs = torch.empty(B, dtype=self.dtype, device=self.device) if want_logabs else None
-        grad = torch.empty_like(p) if want_grad else None
-        check(self._lib.aiqmc_local_energy(self._h, _ptr(p), B, _ptr(el), _ptr(logabs), _ptr(grad),
-                                           _stream(self.device)), "aiqmc_local_energy")
-        return el, logabs, grad
+        return self._local_energy("aiqmc_local_energy", pos, want_logabs, want_grad, out)
 
     def local_energy_complex(self, pos: torch.Tensor) -> torch.Tensor:
         """complex_output=True local energy (hamiltonian.py:110-130): V - 1/2 [lap log|psi| + i lap theta
@@ -991,61 +998,43 @@ class Context:
         complex tensor [B] (complex64 for a float32 context)."""
         p = self._pos(pos)
         B = p.shape[0]
-        re = torch.empty(B, dtype=self.dtype, device=self.device)
-        im = torch.empty(B, dtype=self.dtype, device=self.device)
-        check(self._lib.aiqmc_local_energy_complex(self._h, _ptr(p), B, _ptr(re), _ptr(im), _stream(self.device)),
-              "aiqmc_local_energy_complex")
+        re, im = self._new(B), self._new(B)
+        self._call("aiqmc_local_energy_complex", p, B, re, im)
         return torch.complex(re, im)
 
     def local_energy_forward_mode(self, pos: torch.Tensor, want_logabs: bool = False, want_grad: bool = False):
         """Diagnostics: the same quantity through the single-launch forward-Laplacian kernel."""
-        p = self._pos(pos)
-        B = p.shape[0]
-        el = torch.empty(B, dtype=self.dtype, device=self.device)
-        logabs = torch.empty(B, dtype=self.dtype, device=self.device) if want_logabs else None
-        grad = torch.empty_like(p) if want_grad else None
-        check(self._lib.aiqmc_debug_local_energy_forward(self._h, _ptr(p), B, _ptr(el), _ptr(logabs), _ptr(grad),
-                                                         _stream(self.device)), "aiqmc_debug_local_energy_forward")
-        return el, logabs, grad
+        return self._local_energy("aiqmc_debug_local_energy_forward", pos, want_logabs, want_grad)
 
-    def _param_grad(self, fn, what: str, pos: torch.Tensor, weights: Optional[torch.Tensor], want_value: bool):
+    def _param_grad(self, name: str, pos: torch.Tensor, weights: Optional[torch.Tensor], want_value: bool):
         p = self._pos(pos)
         B = p.shape[0]
-        w = None
-        if weights is not None:
-            w = weights.to(self.device, self.dtype).contiguous()
-            if w.numel() != B:
-                raise ValueError("weights must have one entry per walker")
-            out = torch.empty(self.nparams, dtype=self.dtype, device=self.device)
-        else:
-            out = torch.empty(B, self.nparams, dtype=self.dtype, device=self.device)
-        val = torch.empty(B, dtype=self.dtype, device=self.device) if want_value else None
-        check(fn(self._h, _ptr(p), B, _ptr(w), _ptr(out), _ptr(val), _stream(self.device)), what)
+        w = self._weights(weights, B)
+        out = self._new(self.nparams) if w is not None else self._new(B, self.nparams)
+        val = self._new(B) if want_value else None
+        self._call(name, p, B, w, out, val)
         return (out, val) if want_value else out
 
     def logpsi_param_grad(self, pos: torch.Tensor, weights: Optional[torch.Tensor] = None,
                           want_logabs: bool = False):
         """d log|psi| / d theta in canonical (tree_flatten) order: [B, P] per walker, or [P] =
         sum_b weights[b] d log|psi_b| / d theta when weights [B] are given."""
-        return self._param_grad(self._lib.aiqmc_logpsi_param_grad, "aiqmc_logpsi_param_grad", pos, weights,
-                                want_logabs)
+        return self._param_grad("aiqmc_logpsi_param_grad", pos, weights, want_logabs)
 
     def phase_param_grad(self, pos: torch.Tensor, weights: Optional[torch.Tensor] = None,
                          want_phase: bool = False):
         """d phase / d theta (phase = arg det A), same conventions as logpsi_param_grad."""
-        return self._param_grad(self._lib.aiqmc_phase_param_grad, "aiqmc_phase_param_grad", pos, weights,
-                                want_phase)
+        return self._param_grad("aiqmc_phase_param_grad", pos, weights, want_phase)
 
     def param_grad_weighted(self, pos: torch.Tensor, weights: torch.Tensor, phase: bool = False) -> torch.Tensor:
         """[K, P] = weights [K, B] times d f / d theta (f = log|psi|, or the phase), one gradient pass."""
         p = self._pos(pos)
         B = p.shape[0]
-        w = weights.to(self.device, self.dtype).contiguous()
+        w = self._dev(weights, None)
         if w.dim() != 2 or w.shape[1] != B:
             raise ValueError("weights must be [K, B]")
-        out = torch.empty(w.shape[0], self.nparams, dtype=self.dtype, device=self.device)
-        check(self._lib.aiqmc_param_grad_weighted(self._h, _ptr(p), B, 1 if phase else 0, _ptr(w), w.shape[0],
-                                                  _ptr(out), None, _stream(self.device)), "aiqmc_param_grad_weighted")
+        out = self._new(w.shape[0], self.nparams)
+        self._call("aiqmc_param_grad_weighted", p, B, 1 if phase else 0, w, w.shape[0], out, None)
         return out
 
     # -- DMC (DMC/drift_diffusion.py, S_matrix.py, dmc.py, branch.py) -------------
@@ -1053,37 +1042,16 @@ class Context:
                             offset: int = 0):
         """In-place drift-diffusion step; returns (grad_eff_old, grad_new_eff, tdamp[3] float64)."""
         B = self._inplace(pos, "dmc_drift_diffusion", note="")
-        if B * 3 * self.N != pos.numel():
-            raise ValueError(f"positions must hold whole walkers of 3N={3 * self.N} coordinates")
-        host = gauss1 is not None
-        if host != (gauss2 is not None) or host != (u is not None):
-            raise ValueError("gauss1, gauss2 and u are injected together or not at all")
-        g1 = self._dev(gauss1, B * 3 * self.N) if host else None      # [1, B, 3N]
-        g2 = self._dev(gauss2, B * self.N * 3) if host else None      # [1, B, N, 3] (diagonal blocks)
-        uu = self._dev(u, B * self.N) if host else None               # [1, B, N]
-        go = torch.empty(B, 3 * self.N, dtype=self.dtype, device=self.device)
-        gn = torch.empty_like(go)
+        N = self.N
+        if B * 3 * N != pos.numel():
+            raise ValueError(f"positions must hold whole walkers of 3N={3 * N} coordinates")
+        # gauss1 [1, B, 3N], gauss2 [1, B, N, 3] (diagonal blocks), u [1, B, N]
+        mode, (g1, g2, uu) = self._rng("dmc_drift_diffusion", gauss1=(gauss1, B * 3 * N), gauss2=(gauss2, B * N * 3),
+                                       u=(u, B * N))
+        go, gn = self._new(B, 3 * N), self._new(B, 3 * N)
         td = torch.zeros(3, dtype=torch.float64, device=self.device)
-        check(self._lib.aiqmc_dmc_drift_diffusion(self._h, _ptr(pos), B, float(tstep),
-                                                  AIQMC_RNG_HOST if host else AIQMC_RNG_PHILOX, _ptr(g1), _ptr(g2),
-                                                  _ptr(uu), ctypes.c_uint64(seed), ctypes.c_uint64(offset), _ptr(go),
-                                                  _ptr(gn), _ptr(td), _stream(self.device)), "aiqmc_dmc_drift_diffusion")
+        self._call("aiqmc_dmc_drift_diffusion", pos, B, float(tstep), mode, g1, g2, uu, seed, offset, go, gn, td)
         return go, gn, td
-
-    def _real_dev(self, t, n: int, what: str) -> torch.Tensor:
-        t = torch.as_tensor(t)
-        t = t.real if torch.is_complex(t) else t
-        t = t.to(self.device, self.dtype).contiguous()
-        if t.numel() != n:
-            raise ValueError(f"{what}: expected {n} values, got {t.numel()}")
-        return t
-
-    def _grad_arg(self, g: torch.Tensor, B: int, what: str) -> torch.Tensor:
-        if not (isinstance(g, torch.Tensor) and g.is_cuda and g.dtype == self.dtype):
-            raise ValueError(f"{what} must be a device tensor of the context dtype {self.dtype}")
-        if g.numel() != B * 3 * self.N:
-            raise ValueError(f"{what}: expected {B * 3 * self.N} values, got {g.numel()}")
-        return g.contiguous()
 
     def dmc_weights(self, weights: torch.Tensor, eloc_old, eloc_new, grad_eff_old, grad_new_eff, tdamp, tstep: float,
                     e_trial, e_est, branchcut: float, cut_minima: Optional[torch.Tensor] = None):
@@ -1093,18 +1061,18 @@ class Context:
         B = weights.numel()
         if not (weights.is_cuda and weights.dtype == self.dtype and weights.is_contiguous()):
             raise ValueError("weights must be a contiguous device tensor of the context dtype (updated in place)")
-        eo = self._real_dev(eloc_old, B, "eloc_old")
-        en = self._real_dev(eloc_new, B, "eloc_new")
+        eo = self._dev(eloc_old, B, "eloc_old", real=True)
+        en = self._dev(eloc_new, B, "eloc_new", real=True)
         go = self._grad_arg(grad_eff_old, B, "grad_eff_old")
         gn = self._grad_arg(grad_new_eff, B, "grad_new_eff")
         if not (isinstance(tdamp, torch.Tensor) and tdamp.is_cuda and tdamp.dtype == torch.float64 and tdamp.numel() == 3):
             raise ValueError("tdamp must be the device float64[3] of dmc_drift_diffusion")
         et_b = ee_b = None
         if torch.is_tensor(e_trial) and e_trial.numel() > 1:
-            et_b = self._real_dev(e_trial, B, "e_trial")
+            et_b = self._dev(e_trial, B, "e_trial", real=True)
             e_trial = 0.0
         if torch.is_tensor(e_est) and e_est.numel() > 1:
-            ee_b = self._real_dev(e_est, B, "e_est")
+            ee_b = self._dev(e_est, B, "e_est", real=True)
             e_est = 0.0
         e_trial = complex(e_trial).real if not torch.is_tensor(e_trial) else complex(e_trial.item()).real
         e_est = complex(e_est).real if not torch.is_tensor(e_est) else complex(e_est.item()).real
@@ -1113,37 +1081,31 @@ class Context:
             if not (cut_minima.is_cuda and cut_minima.dtype == torch.float64 and cut_minima.numel() == 2):
                 raise ValueError("cut_minima must be a device float64[2]")
             cm = cut_minima.contiguous()
-        check(self._lib.aiqmc_dmc_weights_ex(self._h, B, _ptr(eo), _ptr(en), _ptr(go), _ptr(gn), _ptr(tdamp),
-                                             float(tstep), _ptr(et_b), _ptr(ee_b), float(e_trial), float(e_est),
-                                             float(branchcut), _ptr(cm), _ptr(weights), _stream(self.device)),
-              "aiqmc_dmc_weights_ex")
+        self._call("aiqmc_dmc_weights_ex", B, eo, en, go, gn, tdamp, float(tstep), et_b, ee_b, float(e_trial),
+                   float(e_est), float(branchcut), cm, weights)
         return weights
 
     def dmc_cut_minima(self, eloc_old, eloc_new, e_est, branchcut: float) -> torch.Tensor:
         """This batch's e_cut minima [2] (float64, device) for eloc_old / eloc_new (S_matrix.py:21-22);
         a multi-GPU driver all-reduces them with MIN (the reference's jnp.min spans all devices)."""
-        eo = torch.as_tensor(eloc_old)
+        eo = self._dev(eloc_old, None, real=True)
         B = eo.numel()
-        eo = self._real_dev(eo, B, "eloc_old")
-        en = self._real_dev(eloc_new, B, "eloc_new")
+        en = self._dev(eloc_new, B, "eloc_new", real=True)
         ee_b = None
         if torch.is_tensor(e_est) and e_est.numel() > 1:
-            ee_b = self._real_dev(e_est, B, "e_est")
+            ee_b = self._dev(e_est, B, "e_est", real=True)
             e_est = 0.0
         e_est = complex(e_est).real if not torch.is_tensor(e_est) else complex(e_est.item()).real
-        out = torch.empty(2, dtype=torch.float64, device=self.device)
-        check(self._lib.aiqmc_dmc_cut_minima(self._h, B, _ptr(eo), _ptr(en), _ptr(ee_b), float(e_est),
-                                             float(branchcut), _ptr(out), _stream(self.device)), "aiqmc_dmc_cut_minima")
+        out = self._new(2, dtype=torch.float64)
+        self._call("aiqmc_dmc_cut_minima", B, eo, en, ee_b, float(e_est), float(branchcut), out)
         return out
 
     def dmc_branch(self, weights: torch.Tensor, u: float):
         """Stochastic comb (branch.py:10-33): (new uniform weight [1], newinds [B] int32)."""
-        B = weights.numel()
-        w = weights.to(self.device, self.dtype).contiguous()
-        idx = torch.empty(B, dtype=torch.int32, device=self.device)
-        wo = torch.empty(1, dtype=self.dtype, device=self.device)
-        check(self._lib.aiqmc_dmc_branch(self._h, B, _ptr(w), float(u), _ptr(idx), _ptr(wo), _stream(self.device)),
-              "aiqmc_dmc_branch")
+        w = self._dev(weights, None)
+        B = w.numel()
+        idx, wo = self._new(B, dtype=torch.int32), self._new(1)
+        self._call("aiqmc_dmc_branch", B, w, float(u), idx, wo)
         return wo, idx
 
     def dmc_tmoves(self, pos: torch.Tensor, tstep: float, rot=None, u_sel=None, u_acc=None, seed: int = 0,
@@ -1151,23 +1113,10 @@ class Context:
         """In-place T-moves (DMC/Tmoves.py:32-225) on `pos`; returns the acceptance [B, N].
         rot [B,3,3], u_sel [B], u_acc [B,N]: injected draws (parity mode); all None: Philox."""
         B = self._inplace(pos, "dmc_tmoves")
-        host = rot is not None
-        if host != (u_sel is not None) or host != (u_acc is not None):
-            raise ValueError("rot, u_sel and u_acc are injected together or not at all")
-        dev = lambda t, n: None if t is None else self._dev(t, n)
-        r, us, ua = dev(rot, 9 * B), dev(u_sel, B), dev(u_acc, B * self.N)
-        acc = torch.empty(B, self.N, dtype=self.dtype, device=self.device)
-        check(self._lib.aiqmc_dmc_tmoves(self._h, _ptr(pos), B, float(tstep), AIQMC_RNG_HOST if host else
-                                         AIQMC_RNG_PHILOX, _ptr(r), _ptr(us), _ptr(ua), ctypes.c_uint64(seed),
-                                         ctypes.c_uint64(offset), _ptr(acc), _stream(self.device)),
-              "aiqmc_dmc_tmoves")
+        mode, (r, us, ua) = self._rng("dmc_tmoves", rot=(rot, 9 * B), u_sel=(u_sel, B), u_acc=(u_acc, B * self.N))
+        acc = self._new(B, self.N)
+        self._call("aiqmc_dmc_tmoves", pos, B, float(tstep), mode, r, us, ua, seed, offset, acc)
         return acc
-
-    def _dev(self, t, n: int) -> torch.Tensor:
-        t = torch.as_tensor(t).to(self.device, self.dtype).contiguous()
-        if t.numel() != n:
-            raise ValueError(f"expected {n} values, got {t.numel()}")
-        return t
 
     def _ecp_arrays(self, tables, list_l: int):
         """The six tables as private read-only float64 arrays in the C-ABI's shapes ([A][KL],
@@ -1188,8 +1137,7 @@ class Context:
         dp = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
         e.rn_local, e.local_coes, e.local_exps = (dp(a) for a in arr[:3])
         e.rn_non_local, e.non_local_coes, e.non_local_exps = (dp(a) for a in arr[3:])
-        with torch.cuda.device(self.device):
-            rc = self._lib.aiqmc_set_ecp(self._h, ctypes.byref(e))
+        rc = self._call("aiqmc_set_ecp", ctypes.byref(e), stream=False, raw=True)   # raw: the code is looked at first
         if rc == AIQMC_EHIP:   # the library dropped its tables; a refused argument leaves the old ones in place
             self._ecp_keep, self._ecp_token = None, None
         check(rc, "aiqmc_set_ecp")
@@ -1231,46 +1179,27 @@ class Context:
         complex_output: with the kinetic energy's phase terms (pphamiltonian.py:84-104)."""
         p = self._pos(pos)
         B = p.shape[0]
-        er = torch.empty(B, dtype=self.dtype, device=self.device)
-        ei = torch.empty(B, dtype=self.dtype, device=self.device)
-        r = self._rot(rot, B)
-        nq = B * self.N * self.A * ECP_NQ
-        lq = torch.empty(nq, dtype=self.dtype, device=self.device) if want_quadrature else None
-        pq = torch.empty(nq, dtype=self.dtype, device=self.device) if want_quadrature else None
-        mode = AIQMC_RNG_HOST if r is not None else AIQMC_RNG_PHILOX
+        er, ei = self._new(B), self._new(B)
+        mode, (r,) = self._rng("local_energy_ecp", rot=(rot, 9 * B))
         if complex_output:
             if want_quadrature:
                 raise ValueError("want_quadrature is not available with complex_output")
-            check(self._lib.aiqmc_local_energy_ecp_complex(self._h, _ptr(p), B, mode, _ptr(r), ctypes.c_uint64(seed),
-                                                           ctypes.c_uint64(offset), _ptr(er), _ptr(ei),
-                                                           _stream(self.device)), "aiqmc_local_energy_ecp_complex")
-        else:
-            check(self._lib.aiqmc_local_energy_ecp(self._h, _ptr(p), B, mode, _ptr(r), ctypes.c_uint64(seed),
-                                                   ctypes.c_uint64(offset), _ptr(er), _ptr(ei), _ptr(lq), _ptr(pq),
-                                                   _stream(self.device)), "aiqmc_local_energy_ecp")
+            self._call("aiqmc_local_energy_ecp_complex", p, B, mode, r, seed, offset, er, ei)
+            return torch.complex(er, ei)
+        q = (B, self.N, self.A, ECP_NQ)
+        lq, pq = (self._new(q), self._new(q)) if want_quadrature else (None, None)
+        self._call("aiqmc_local_energy_ecp", p, B, mode, r, seed, offset, er, ei, lq, pq)
         e = torch.complex(er, ei)
-        if want_quadrature:
-            return e, lq.reshape(B, self.N, self.A, ECP_NQ), pq.reshape(B, self.N, self.A, ECP_NQ)
-        return e
+        return (e, lq, pq) if want_quadrature else e
 
     def mc_step(self, pos: torch.Tensor, nsteps: int, tstep: float, gauss1=None, gauss2=None, u=None,
                 seed: int = 0, offset: int = 0, count_accepts: bool = False):
         """In-place Metropolis on `pos` (must be a contiguous device tensor of ctx dtype)."""
         B = self._inplace(pos, "mc_step")
-        host = gauss1 is not None
+        n = int(nsteps) * B * self.N
+        mode, (g1, g2, uu) = self._rng("mc_step", gauss1=(gauss1, 3 * n), gauss2=(gauss2, 3 * n), u=(u, n))
         acc = torch.zeros(B, dtype=torch.int32, device=self.device) if count_accepts else None
-        if host:
-            g1 = gauss1.to(self.device, self.dtype).contiguous()
-            g2 = gauss2.to(self.device, self.dtype).contiguous()
-            uu = u.to(self.device, self.dtype).contiguous()
-            if g1.numel() != nsteps * B * 3 * self.N or g2.numel() != nsteps * B * self.N * 3 or \
-                    uu.numel() != nsteps * B * self.N:
-                raise ValueError("host draws have the wrong size")
-        else:
-            g1 = g2 = uu = None
-        check(self._lib.aiqmc_mc_step(self._h, _ptr(pos), B, int(nsteps), float(tstep),
-                                      AIQMC_RNG_HOST if host else AIQMC_RNG_PHILOX,
-                                      _ptr(g1), _ptr(g2), _ptr(uu), ctypes.c_uint64(seed),
-                                      ctypes.c_uint64(offset), _ptr(acc), _stream(self.device)),
-              "aiqmc_mc_step")
+        self._call("aiqmc_mc_step", pos, B, int(nsteps), float(tstep), mode, g1, g2, uu, seed, offset, acc)
         return acc
+
+

@@ -325,7 +325,7 @@ class DensityAccumulator:
             ok = torch.ones(B, dtype=torch.bool, device=dev)
         else:
             w = torch.as_tensor(weights).to(dev, T).reshape(-1).double()
-            if w.numel() != B:
+            if w.numel() != B:   # no context on the host path: the message of _lib.Context._weights
                 raise ValueError("weights must have one entry per walker")
             ok = (w >= 0.0) & (w < _MAX_WEIGHT)
             q = torch.where(ok, torch.round(torch.where(ok, w, torch.zeros_like(w)) * float(_ONE)),

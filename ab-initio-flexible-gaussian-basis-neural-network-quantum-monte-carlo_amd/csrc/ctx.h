@@ -1,5 +1,6 @@
-// ctx.h -- host-side context + per-shape dispatch table shared by the C-ABI translation units
-// (aiqmc.hip, observables.hip) and the per-shape kernel TUs (shape.hip).
+// ctx.h -- host-side context + per-shape dispatch table shared by every C-ABI translation unit that
+// takes a context (aiqmc.hip, dmc.hip, debug.hip, observables.hip, components.hip, density.hip,
+// corrsamples.hip, rdm.hip) and the per-shape kernel TUs (shape.hip); api_util.h includes it.
 #pragma once
 #include <hip/hip_runtime.h>
 

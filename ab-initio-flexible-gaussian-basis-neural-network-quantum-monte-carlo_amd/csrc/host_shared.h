@@ -1,5 +1,5 @@
 // host_shared.h -- the host helpers that more than one context translation unit calls (aiqmc.hip,
-// dmc.hip, debug.hip).  Each is defined in the unit named beside it; none is exported (hidden
+// dmc.hip, debug.hip, observables.hip, rdm.hip).  Each is defined in the unit named beside it; none is exported (hidden
 // visibility: the library's dynamic symbol table is the C-ABI of include/aiqmc.h).
 #pragma once
 #include "api_util.h"
@@ -56,6 +56,13 @@ double* dmc_scratch(aiqmc_ctx* c);
 // ones (g1 == nullptr) to dmc[1] and tdamp to dmc[2], in block order
 void dmc_coord_sum(aiqmc_ctx* c, const void* pos, const void* g1, double tstep, int n, double* dscr, double* dmc,
                    hipStream_t s);
+
+// ---- observables.hip
+// the d_obs_* workspace of one chunk of nconf configurations (x, log|psi|, phase, walker cache)
+int ensure_obs(aiqmc_ctx* c, int nconf, const ShapeOps& ops);
+// the value launch over the nconf configurations in d_obs_x: log|psi| to d_obs_lp, the phase to
+// d_obs_ph, with aiqmc_logpsi's arguments (the same kernels and bits)
+void obs_values(aiqmc_ctx* c, const ShapeOps& ops, int nconf, hipStream_t s);
 
 #pragma GCC visibility pop
 }  // namespace aq_host

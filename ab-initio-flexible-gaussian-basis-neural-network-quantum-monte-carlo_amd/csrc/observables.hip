@@ -26,7 +26,7 @@
 #include <string>
 
 #include "aiqmc.h"
-#include "api_util.h"
+#include "host_shared.h"
 
 using namespace aq;
 
@@ -97,16 +97,6 @@ __global__ __launch_bounds__(256) void k_dipole(const T* __restrict__ pos, int N
   mu[t] = (T)(c == 0 ? n0 : (c == 1 ? n1 : n2)) - s;
 }
 
-// the workspace of one chunk of nconf configurations
-int obs_ensure(aiqmc_ctx* c, int nconf, const ShapeOps& ops) {
-  const size_t s = elem_size(c), n = (size_t)nconf;
-  HIPCHK(c->d_obs_x.reserve(n * 3 * c->N * s));
-  HIPCHK(c->d_obs_lp.reserve(n * s));
-  HIPCHK(c->d_obs_ph.reserve(n * s));
-  HIPCHK(c->d_obs_wc.reserve(n * ops.wcache_n * s));
-  return 0;
-}
-
 template <typename T>
 void s2_reduce_launch(int G, int nw, const void* lp, const void* ph, int K, int b0, double diag, void* re, void* im,
                       void* dl, void* dp, hipStream_t s) {
@@ -123,6 +113,21 @@ void s2_reduce_launch(int G, int nw, const void* lp, const void* ph, int K, int 
 
 }  // namespace
 
+// host_shared.h: the chunk workspace and the value launch, shared with rdm.hip
+int aq_host::ensure_obs(aiqmc_ctx* c, int nconf, const ShapeOps& ops) {
+  const size_t s = elem_size(c), n = (size_t)nconf;
+  HIPCHK(c->d_obs_x.reserve(n * 3 * c->N * s));
+  HIPCHK(c->d_obs_lp.reserve(n * s));
+  HIPCHK(c->d_obs_ph.reserve(n * s));
+  HIPCHK(c->d_obs_wc.reserve(n * ops.wcache_n * s));
+  return 0;
+}
+void aq_host::obs_values(aiqmc_ctx* c, const ShapeOps& ops, int nconf, hipStream_t s) {
+  KArgs ka = walker_args(c, c->d_obs_x.as(), nconf, c->d_obs_lp.as(), c->d_obs_wc);   // aiqmc_logpsi's arguments
+  ka.phase = c->d_obs_ph.as();
+  ops.walker(c->dtype, MODE_GRAD, ka, nconf, s);
+}
+
 extern "C" {
 
 int aiqmc_spin_squared(aiqmc_ctx* c, const void* pos, int32_t B, void* s2_re, void* s2_im, void* dlogabs,
@@ -134,8 +139,7 @@ int aiqmc_spin_squared(aiqmc_ctx* c, const void* pos, int32_t B, void* s2_re, vo
   int W = c->obs_chunk / (K + 1);   // walkers per chunk
   if (W < 1) W = 1;
   if (W > B) W = B;
-  int rc = obs_ensure(c, W * (K + 1), ops);
-  if (rc) return rc;
+  if (int rc = aq_host::ensure_obs(c, W * (K + 1), ops)) return rc;
   const int na = c->nup > c->ndn ? c->nup : c->ndn, nb = c->nup + c->ndn - na;
   const double sz = 0.5 * (na - nb), diag = sz * (sz + 1.0) + nb;
   int G = 4;
@@ -145,13 +149,11 @@ int aiqmc_spin_squared(aiqmc_ctx* c, const void* pos, int32_t B, void* s2_re, vo
   for (int b0 = 0; b0 < B; b0 += W) {
     const int nw = B - b0 < W ? B - b0 : W;
     const int nconf = nw * (K + 1);
-    KArgs ka = walker_args(c, c->d_obs_x.as(), nconf, lp, c->d_obs_wc);   // the arguments of aiqmc_logpsi
-    ka.phase = ph;
     by_dtype(c->dtype, [&](auto t) {
       using T = decltype(t);
       k_s2_exchange<T><<<blocks((int64_t)nconf * c->N, 256), dim3(256), 0, s>>>(
           (const T*)pos, c->d_rowsrc.as<int>(), c->N, c->nup, c->ndn, b0, nconf, c->d_obs_x.as<T>());
-      ops.walker(c->dtype, MODE_GRAD, ka, nconf, s);
+      aq_host::obs_values(c, ops, nconf, s);
       s2_reduce_launch<T>(G, nw, lp, ph, K, b0, diag, s2_re, s2_im, dlogabs, dphase, s);
     });
   }

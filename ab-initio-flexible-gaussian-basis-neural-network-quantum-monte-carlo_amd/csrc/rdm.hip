@@ -33,7 +33,7 @@
 #include <vector>
 
 #include "aiqmc.h"
-#include "api_util.h"
+#include "host_shared.h"
 
 using namespace aq;
 
@@ -443,12 +443,9 @@ int aiqmc_rdm_accumulate(aiqmc_ctx* c, const void* pos, int32_t B, int32_t S, in
     if (W > B) W = B;
   }
   if ((int64_t)W * K1 > INT32_MAX) return fail(AIQMC_EINVAL, "too many moved configurations for one chunk");
-  const size_t es = elem_size(c), nc = (size_t)W * K1;
+  const size_t es = elem_size(c);
   const int G = (W + AIQMC_RDM_GROUP - 1) / AIQMC_RDM_GROUP, nt = 2 * K * K * 2;
-  HIPCHK(c->d_obs_x.reserve(nc * 3 * N * es));
-  HIPCHK(c->d_obs_lp.reserve(nc * es));
-  HIPCHK(c->d_obs_ph.reserve(nc * es));
-  HIPCHK(c->d_obs_wc.reserve(nc * ops.wcache_n * es));
+  if (int rc = aq_host::ensure_obs(c, W * K1, ops)) return rc;
   HIPCHK(c->d_rdm_rp.reserve((size_t)W * S * 3 * es));
   HIPCHK(c->d_rdm_iq.reserve((size_t)W * S * es));
   HIPCHK(c->d_rdm_pe.reserve((size_t)W * N * K * es));
@@ -463,8 +460,6 @@ int aiqmc_rdm_accumulate(aiqmc_ctx* c, const void* pos, int32_t B, int32_t S, in
   for (int b0 = 0; b0 < B; b0 += W) {
     const int nw = B - b0 < W ? B - b0 : W;
     const int nconf = nw * K1, ng = (nw + AIQMC_RDM_GROUP - 1) / AIQMC_RDM_GROUP;
-    KArgs ka = walker_args(c, c->d_obs_x.as(), nconf, lp, c->d_obs_wc);   // the arguments of aiqmc_logpsi
-    ka.phase = ph;
     by_dtype(c->dtype, [&](auto t) {
       using T = decltype(t);
       T *rp = c->d_rdm_rp.as<T>(), *pe = c->d_rdm_pe.as<T>(), *pp = c->d_rdm_pp.as<T>(), *f = c->d_rdm_f.as<T>();
@@ -473,7 +468,7 @@ int aiqmc_rdm_accumulate(aiqmc_ctx* c, const void* pos, int32_t B, int32_t S, in
           (T*)rprime_out);
       k_rdm_build<T><<<blocks((int64_t)nconf * N, 256), dim3(256), 0, s>>>((const T*)pos, rp, N, S, b0, nconf,
                                                                            c->d_obs_x.as<T>());
-      ops.walker(c->dtype, MODE_GRAD, ka, nconf, s);
+      aq_host::obs_values(c, ops, nconf, s);
       k_rdm_ratio<T><<<blocks((int64_t)nw * S * N, 256), dim3(256), 0, s>>>(
           (const T*)lp, (const T*)ph, c->d_rdm_iq.as<T>(), (const T*)weights, N, S, b0, nw, f, (T*)ratio_out);
       const T* xw = (const T*)pos + (size_t)b0 * 3 * N;

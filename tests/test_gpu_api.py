@@ -319,3 +319,56 @@ def test_fused_loss_weights_match_torch_path(complex_e, clip, center, dtype):
     np.testing.assert_allclose(st[0].item(), float(m.real), rtol=1e-12)
     np.testing.assert_allclose(st[2].item(), float(var), rtol=1e-12)
     np.testing.assert_allclose(st[3].item(), float(dc.real), rtol=1e-12)
+
+
+def _h2_walkers(dtype, B=8):
+    """An H2 context with parameters, B walkers and one sweep of injected draws."""
+    from oracle import system
+    from aiqmc import _lib
+    s = system.make_system("H2")
+    assert (s.nelectrons, s.natoms) == (2, 2)
+    ctx = _lib.Context.for_system(s, dtype)
+    ctx.set_params(system.flatten_params(system.init_params(np.random.default_rng(3), s, randomize_aux=True)))
+    rng = np.random.default_rng(17)
+    pos = torch.tensor(system.init_electrons(rng, s.atoms, s.charges, B, 1.0), dtype=dtype, device="cuda")
+    N = s.nelectrons
+    draws = dict(gauss1=torch.tensor(rng.standard_normal((1, B, 3 * N))),
+                 gauss2=torch.tensor(rng.standard_normal((1, B, N, 3))), u=torch.tensor(rng.uniform(size=(1, B, N))))
+    torch.cuda.synchronize()
+    return ctx, pos.contiguous(), draws
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float64])
+def test_calls_take_the_stream_at_call_time(dtype):
+    """logpsi, local_energy and one mc_step sweep with injected draws under torch.cuda.stream(side)
+    give the bits of the same calls on the default stream: the binding's call path reads the
+    current stream when it is called."""
+    ctx, pos, draws = _h2_walkers(dtype)
+
+    def run():
+        la, ph = ctx.logpsi(pos)
+        el, _, _ = ctx.local_energy(pos)
+        x = pos.clone()
+        acc = ctx.mc_step(x, 1, 0.05, count_accepts=True, **draws)
+        return la, ph, el, x, acc
+
+    ref = run()
+    torch.cuda.synchronize()
+    side = torch.cuda.Stream()
+    with torch.cuda.stream(side):
+        assert torch.cuda.current_stream() == side
+        out = run()
+    assert torch.cuda.current_stream() != side
+    side.synchronize()
+    assert not torch.equal(ref[3], pos)            # the sweep moved walkers
+    for a, b in zip(ref, out):
+        assert torch.equal(a, b)
+
+
+def test_mc_step_refuses_half_given_draws():
+    ctx, pos, draws = _h2_walkers(torch.float64)
+    x = pos.clone()
+    with pytest.raises(ValueError, match="gauss1, gauss2 and u are injected together or not at all"):
+        ctx.mc_step(x, 1, 0.05, gauss1=draws["gauss1"])
+    torch.cuda.synchronize()
+    assert torch.equal(x, pos)

@@ -196,6 +196,7 @@ _SIGNATURES = {
     "aiqmc_debug_local_energy_forward": (_int, [_vp, _vp, _i32, _vp, _vp, _vp, _vp]),
     "aiqmc_debug_limdrift_factor": (_int, [_vp, _vp, _i32, _dbl, _i32, _p(_dbl), _vp]),
     "aiqmc_debug_launch_lds": (_int, [_i32, _i32, _i32, _i32, _p(_i32), _p(_i32)]),
+    "aiqmc_debug_launch_row": (_int, [_vp, _i32, _i32, _p(_i32)]),
     "aiqmc_debug_phase_cycles": (_int, [_vp, _vp]),
     "aiqmc_debug_set_ablate": (_int, [_vp, _i32]),
     "aiqmc_debug_set_fuse_accept": (_int, [_vp, _i32]),
@@ -263,6 +264,11 @@ def _dt(t) -> int:
 
 
 LDS_KINDS = ("proposal", "walker", "adjoint", "lap", "pgrad", "fwdlap")   # AIQMC_LDS_* order
+
+
+# AIQMC_LAUNCH_* order: what a walker launch is (csrc/launch_route.h)
+LAUNCH_KINDS = ("walker_value", "walker_orbitals", "walker_grad", "sweep_walker", "proposal", "quadrature",
+                "lap_forward", "grad_forward")
 
 
 def launch_lds(nelectrons: int, natoms: int, dtype=torch.float32) -> dict:
@@ -922,6 +928,15 @@ class Context:
     def set_packed_walkers(self, on: bool):
         """Diagnostics: walker launches of N <= 8 several per wave (default) or one wave each."""
         self._call("aiqmc_debug_set_packed_walkers", int(bool(on)), stream=False)
+
+    def launch_row(self, kind, nconf: int) -> int:
+        """Diagnostics: the row (1..8) of the walker-launch table of csrc/shape.hip that a launch of
+        `kind` (a LAUNCH_KINDS name or its index) over nconf configurations reaches with this
+        context's current switches.  Launches nothing."""
+        k = LAUNCH_KINDS.index(kind) if isinstance(kind, str) else int(kind)
+        row = ctypes.c_int32(0)
+        self._call("aiqmc_debug_launch_row", k, int(nconf), ctypes.byref(row), stream=False)
+        return row.value
 
     def set_quad_pivoted(self, on: bool):
         """Diagnostics: the N <= 8 ECP quadrature launch factors every configuration with partial

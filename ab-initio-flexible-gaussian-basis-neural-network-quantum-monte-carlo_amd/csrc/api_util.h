@@ -7,6 +7,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
 #include <cstring>
 #include <string>
 
@@ -63,7 +64,16 @@ inline auto by_dtype(int dtype, F&& f) {
 // grid of n threads in workgroups of `per`
 inline dim3 blocks(int64_t n, int per) { return dim3((unsigned)((n + per - 1) / per)); }
 
-// ---- KArgs builders: what every launch of a kind shares; the call site adds its outputs and flags
+// The layout the kernels were compiled against: KArgs keeps its size and the offsets of what follows
+// its reserved pair (walker_kernel.h) until a kernel-side change moves them on purpose.
+static_assert(sizeof(KArgs) == 368 && offsetof(KArgs, reserved0) == 284 && offsetof(KArgs, reserved1) == 288 &&
+                  offsetof(KArgs, quad_pivoted) == 292 && offsetof(KArgs, wcache) == 296 && offsetof(KArgs, ecache) == 304 &&
+                  offsetof(KArgs, lapcache) == 312 && offsetof(KArgs, logabs) == 320 && offsetof(KArgs, phase) == 328 &&
+                  offsetof(KArgs, grad) == 336 && offsetof(KArgs, el) == 344 && offsetof(KArgs, sumsq) == 352 &&
+                  offsetof(KArgs, gown) == 360,
+              "KArgs layout changed");
+
+// ---- KArgs builders: what every launch of a kind shares; the call site adds its outputs
 // the context's part of every launch
 inline KArgs base_args(const aiqmc_ctx* c) {
   KArgs ka;
@@ -71,7 +81,6 @@ inline KArgs base_args(const aiqmc_ctx* c) {
   ka.nup = c->nup;
   ka.rowsrc = c->d_rowsrc.as<int>();
   ka.prm = c->d_prm.as();
-  ka.one_wave = c->packed_walkers ? 0 : 1;
   ka.quad_pivoted = c->quad_pivoted;
   return ka;
 }
@@ -84,20 +93,40 @@ inline KArgs conf_args(const aiqmc_ctx* c, const void* pos, int n, void* logabs)
   ka.logabs = logabs;
   return ka;
 }
-// walker launch over B configurations at pos; the kernel keeps its electron-local Jacobians (and
-// what the proposals re-use) in the walker cache wc
-inline KArgs walker_args(const aiqmc_ctx* c, const void* pos, int B, void* logabs, const DevBuf& wc) {
-  KArgs ka = conf_args(c, pos, B, logabs);
-  ka.wcache = wc.as();
-  return ka;
+// The context's part of the routing options (launch_route.h); mc_sweep adds `split`.
+inline aq::LaunchOpts launch_opts(const aiqmc_ctx* c) {
+  aq::LaunchOpts o;
+  o.packed = c->packed_walkers != 0;
+  o.reuse = c->reuse;
+  o.ablate = c->ablate != 0;
+  o.env_split = c->env_walk_split;
+  o.env_quad_grad = c->env_quad_grad;
+  return o;
 }
-// proposal launch: n single-electron-moved configurations of the walkers at pos.  With proposal
-// reuse they come from the walker cache and the moved electrons' stage in ec (the caller runs
-// ops.moved first); without, each takes a scratch cache of the walker layout (d_wcp) and no ecache.
-inline KArgs proposal_args(const aiqmc_ctx* c, const void* pos, int n, void* logabs, const DevBuf& ec) {
-  KArgs kp = conf_args(c, pos, n, logabs);
-  kp.proposal = 1;
-  kp.wcache = c->reuse ? c->d_wc.as() : c->d_wcp.as();
-  kp.ecache = c->reuse ? ec.as() : nullptr;
-  return kp;
+// A walker launch (ops.walker) of `kind` over n configurations, with the KArgs fields the kind
+// implies.  The walker kinds run the n configurations at pos; the kernel keeps its electron-local
+// Jacobians (and what the proposals re-use) in the walker cache `cache`.  Proposal and Quadrature
+// run n single-electron-moved configurations of the walkers at pos: with proposal reuse from the
+// walker cache and the moved electrons' stage in `cache` (the caller runs ops.moved first);
+// without, each takes a scratch cache of the walker layout (d_wcp) and no ecache.  The forward
+// kinds take no cache.
+inline WalkerCall launch_args(const aiqmc_ctx* c, aq::Launch kind, const void* pos, int n, void* logabs,
+                              const DevBuf* cache = nullptr) {
+  WalkerCall w{kind, launch_opts(c), conf_args(c, pos, n, logabs)};
+  KArgs& ka = w.ka;
+  switch (kind) {
+    case aq::Launch::WalkerOrbitals: ka.value_only = 1; [[fallthrough]];
+    case aq::Launch::WalkerValue:
+    case aq::Launch::WalkerGrad:
+    case aq::Launch::SweepWalker: ka.wcache = cache->as(); break;
+    case aq::Launch::Quadrature: ka.value_only = 1; [[fallthrough]];
+    case aq::Launch::Proposal:
+      ka.proposal = 1;
+      ka.wcache = c->reuse ? c->d_wc.as() : c->d_wcp.as();
+      ka.ecache = c->reuse ? cache->as() : nullptr;
+      break;
+    case aq::Launch::LapForward:
+    case aq::Launch::GradForward: break;
+  }
+  return w;
 }

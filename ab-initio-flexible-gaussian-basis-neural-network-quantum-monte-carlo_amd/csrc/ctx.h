@@ -11,11 +11,13 @@
 
 #include "aiqmc.h"
 #include "devbuf.h"
+#include "launch_route.h"
 #include "param_map.h"
 #include "walker_kernel.h"
 
 using aq::KArgs;
-#define AIQMC_PROF_SLOTS 4
+// aiqmc_profile_read's slots: the launches that timed() brackets (the numbers are the C-ABI's)
+enum ProfSlot { PROF_PROPOSAL = 0, PROF_SWEEP_WALKER = 1, PROF_LOCAL_ENERGY = 2, PROF_QUADRATURE = 3, AIQMC_PROF_SLOTS };
 
 struct aiqmc_ctx {
   int N = 0, A = 0, nup = 0, ndn = 0, dtype = 0, device = 0;
@@ -55,6 +57,7 @@ struct aiqmc_ctx {
   bool tacc_clean[2] = {false, false};                      // bank zeroed (by the last k_accept of a call)
   int lap_waves = 0;                                        // waves per walker of k_walker_lap (0: by batch)
   int ncu = 256;                                            // compute units of the device
+  bool env_walk_split = true, env_quad_grad = true;         // AIQMC_WALK_SPLIT / AIQMC_QUAD_GRAD not 0 (aiqmc_create)
   // pseudopotential (aiqmc_set_ecp / aiqmc_local_energy_ecp, ecp.h)
   bool ecp_set = false;
   int ecp_KL = 0, ecp_KN = 0, ecp_L = 0;
@@ -101,9 +104,17 @@ struct aiqmc_ctx {
 // bytes per element of the context's dtype
 inline size_t elem_size(const aiqmc_ctx* c) { return c->dtype == AIQMC_F32 ? 4 : 8; }
 
+// One walker launch: what it is, the host's options of the routing (launch_route.h) and the kernel
+// arguments.  Built by launch_args (api_util.h); a call site adds its outputs to ka.
+struct WalkerCall {
+  aq::Launch kind;
+  aq::LaunchOpts opts;
+  KArgs ka;
+};
+
 struct ShapeOps {
   int (*set_lds)();
-  void (*walker)(int dtype, int mode, const KArgs& ka, int nconf, hipStream_t s);
+  void (*walker)(int dtype, const WalkerCall& w, int nconf, hipStream_t s);   // the kernel of route(w.kind, ..., w.opts)
   void (*accept)(int dtype, void* pos, const aq::AccArgs& a, int B, hipStream_t s);
   void (*moved)(int dtype, const KArgs& ka, hipStream_t s);   // k_moved_electron over ka.nconf proposals
   // local energy: adjoint pass (k1) + first-derivative pass (k2), walker_lap.h

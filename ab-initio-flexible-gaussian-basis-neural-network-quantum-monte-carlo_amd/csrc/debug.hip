@@ -32,10 +32,10 @@ int aiqmc_debug_local_energy_forward(aiqmc_ctx* c, const void* pos, int32_t B, v
                                      void* stream) {
   AIQMC_ENTER(c, pos, B, ops);
   if (!e_l) return fail(AIQMC_EINVAL, "null e_l");
-  KArgs ka = conf_args(c, pos, B, logabs);
-  ka.el = e_l;
-  ka.grad = grad;
-  ops.walker(c->dtype, MODE_LAP, ka, B, (hipStream_t)stream);
+  WalkerCall w = launch_args(c, Launch::LapForward, pos, B, logabs);
+  w.ka.el = e_l;
+  w.ka.grad = grad;
+  ops.walker(c->dtype, w, B, (hipStream_t)stream);
   HIPCHK(hipGetLastError());
   return AIQMC_OK;
 }
@@ -69,9 +69,9 @@ int aiqmc_debug_logpsi_grad_forward(aiqmc_ctx* c, const void* pos, int32_t B, vo
                                      void* stream) {
   AIQMC_ENTER(c, pos, B, ops);
   if (!grad) return fail(AIQMC_EINVAL, "null grad");
-  KArgs ka = conf_args(c, pos, B, logabs);
-  ka.grad = grad;
-  ops.walker(c->dtype, MODE_GRAD_FWD, ka, B, (hipStream_t)stream);
+  WalkerCall w = launch_args(c, Launch::GradForward, pos, B, logabs);
+  w.ka.grad = grad;
+  ops.walker(c->dtype, w, B, (hipStream_t)stream);
   HIPCHK(hipGetLastError());
   return AIQMC_OK;
 }
@@ -116,6 +116,24 @@ int aiqmc_debug_launch_lds(int32_t nelectrons, int32_t natoms, int32_t dtype, in
   const int d = dtype == AIQMC_F32 ? 0 : 1;
   if (bytes) *bytes = ops.dyn_lds[d][kind];
   if (waves) *waves = ops.wg_waves[d][kind];
+  return AIQMC_OK;
+}
+
+// The row (launch_route.h Row, 1..8) a walker launch of `kind` (Launch, 0..7) over nconf
+// configurations would reach with this context's shape, dtype and current switches; nconf decides
+// only the sweep walker's split, by mc_sweep's batch condition.  Launches nothing.
+static_assert((int)Launch::WalkerValue == AIQMC_LAUNCH_WALKER_VALUE && (int)Launch::WalkerOrbitals == AIQMC_LAUNCH_WALKER_ORBITALS &&
+                  (int)Launch::WalkerGrad == AIQMC_LAUNCH_WALKER_GRAD && (int)Launch::SweepWalker == AIQMC_LAUNCH_SWEEP_WALKER &&
+                  (int)Launch::Proposal == AIQMC_LAUNCH_PROPOSAL && (int)Launch::Quadrature == AIQMC_LAUNCH_QUADRATURE &&
+                  (int)Launch::LapForward == AIQMC_LAUNCH_LAP_FORWARD && (int)Launch::GradForward == AIQMC_LAUNCH_GRAD_FORWARD,
+              "AIQMC_LAUNCH_* of aiqmc.h are aq::Launch");
+int aiqmc_debug_launch_row(aiqmc_ctx* c, int32_t kind, int32_t nconf, int32_t* row) {
+  if (!c || !row) return fail(AIQMC_EINVAL, "null argument");
+  if (kind < 0 || kind >= LAUNCH_KINDS) return fail(AIQMC_EINVAL, "kind must be one of AIQMC_LAUNCH_*");
+  if (nconf < 0) return fail(AIQMC_EINVAL, "negative nconf");
+  LaunchOpts o = launch_opts(c);
+  o.split = sweep_split(c, nconf);
+  *row = (int32_t)route((Launch)kind, c->dtype == AIQMC_F32, c->N, o);
   return AIQMC_OK;
 }
 

@@ -314,14 +314,14 @@ int aiqmc_dmc_drift_diffusion(aiqmc_ctx* c, void* pos, int32_t B, double tstep, 
   rc = mc_sweep(c, ops, s, sw);
   if (rc) return rc;
   // grad_new_eff_s: the gradients at the moved walkers (:103-104)
-  KArgs ka = walker_args(c, pos, B, nullptr, c->d_wc);
-  ka.grad = grad_new_eff;
-  ka.sumsq = c->d_sq.as();
+  WalkerCall w = launch_args(c, Launch::WalkerGrad, pos, B, nullptr, &c->d_wc);
+  w.ka.grad = grad_new_eff;
+  w.ka.sumsq = c->d_sq.as();
   by_dtype(c->dtype, [&](auto t) {
     using T = decltype(t);
     // grad_eff_old: limdrift of the walker gradients of this sweep (drift_diffusion.py:60-61)
     k_scale_grad<T><<<blocks(n, 256), dim3(256), 0, s>>>(c->d_grad.as<T>(), taueff, n, (T*)grad_eff_old);
-    ops.walker(c->dtype, MODE_GRAD, ka, B, s);
+    ops.walker(c->dtype, w, B, s);
     // ... and their limdrift
     launch_taueff(c->dtype, c->d_sq.as(), B, tstep, taueff + 1, s);
     k_scale_grad<T><<<blocks(n, 256), dim3(256), 0, s>>>((const T*)grad_new_eff, taueff + 1, n, (T*)grad_new_eff);

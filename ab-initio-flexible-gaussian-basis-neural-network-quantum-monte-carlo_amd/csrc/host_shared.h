@@ -43,6 +43,8 @@ int ensure_wcp(aiqmc_ctx* c, int64_t n, const ShapeOps& ops);
 int ensure_ecp_ws(aiqmc_ctx* c, int B, const ShapeOps& ops);
 int check_sampling(const double* tstep, int rng_mode, int B, bool have, const char* what);
 int mc_sweep(aiqmc_ctx* c, const ShapeOps& ops, hipStream_t s, const SweepArgs& sw);
+// the batch condition of mc_sweep's two-wave walker launch (LaunchOpts::split) for B walkers
+bool sweep_split(const aiqmc_ctx* c, int B);
 int ecp_quadrature(aiqmc_ctx* c, const ShapeOps& ops, const void* pos, int B, int rng_mode, const void* rot,
                    uint64_t seed, uint64_t offset, void* logabs_q, void* phase_q, aq::EcpArgs& ea, hipStream_t s);
 // k_taueff<dtype> (one workgroup of 1024) over the n sums of squares x: the limdrift factor to *out

@@ -123,9 +123,9 @@ int aq_host::ensure_obs(aiqmc_ctx* c, int nconf, const ShapeOps& ops) {
   return 0;
 }
 void aq_host::obs_values(aiqmc_ctx* c, const ShapeOps& ops, int nconf, hipStream_t s) {
-  KArgs ka = walker_args(c, c->d_obs_x.as(), nconf, c->d_obs_lp.as(), c->d_obs_wc);   // aiqmc_logpsi's arguments
-  ka.phase = c->d_obs_ph.as();
-  ops.walker(c->dtype, MODE_GRAD, ka, nconf, s);
+  WalkerCall w = launch_args(c, Launch::WalkerValue, c->d_obs_x.as(), nconf, c->d_obs_lp.as(), &c->d_obs_wc);   // aiqmc_logpsi's
+  w.ka.phase = c->d_obs_ph.as();
+  ops.walker(c->dtype, w, nconf, s);
 }
 
 extern "C" {

@@ -3,7 +3,6 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdlib>
 #include <cstring>
 
 #include "api_util.h"
@@ -69,8 +68,6 @@ static int set_lds_impl() {   // both dtypes: the attribute belongs to the kerne
   return set_lds_t<double, N, A>();
 }
 
-// MODE_GRAD -> reverse-mode value+gradient kernel (walker_rev.h); MODE_LAP -> forward
-// Laplacian kernel (walker_kernel.h); MODE_GRAD_FWD -> forward-mode gradient (diagnostics).
 // proposal-launch grid: ceil(nconf / wpb) workgroups, padded to a multiple of the 8 XCDs so that
 // xcd_major keeps each walker's proposals on one XCD (the padding workgroups exit at once)
 static inline unsigned prop_blocks(int nconf, int wpb) {
@@ -78,96 +75,65 @@ static inline unsigned prop_blocks(int nconf, int wpb) {
   return wpb > 1 ? (nb + 7u) & ~7u : nb;
 }
 
-// single-electron-moved configurations from the walker cache (quad_small.h): value only (pp
-// quadrature, N <= 8) or value + gradient (Metropolis proposals and walker launches, N <= 4),
-// several configurations per wave
-// AIQMC_WALK_SPLIT=0 keeps small-batch walker launches on one wave per walker (A/B timing)
-static bool walk_split_on() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = std::getenv("AIQMC_WALK_SPLIT");
-    v = (e && e[0] == '0') ? 0 : 1;
-  }
-  return v != 0;
-}
-// AIQMC_QUAD_GRAD=0 routes the packed proposals of 5 <= N <= 8 back to k_walker_rev (A/B timing)
-static bool quad_grad_off() {
-  static const int off = [] {
-    const char* e = std::getenv("AIQMC_QUAD_GRAD");
-    return (e && e[0] == '0') ? 1 : 0;
-  }();
-  return off != 0 && AQ_N > 4;
-}
-
-template <typename T, int N, int A>
-static bool quad_small(const KArgs& ka, int nconf, hipStream_t s) {
-  if constexpr (N <= 8) {   // pp quadrature: 4 (N <= 4) or 2 (N <= 8) configurations per wave
-    if (ka.proposal && ka.ecache && ka.value_only && !ka.orb) {
-      k_quad_value<T, N, A><<<dim3(prop_blocks(nconf, QSlot<N>::NSL)), dim3(64), 0, s>>>(ka);
-      return true;
-    }
-  }
-  if constexpr (N <= 8) {   // Metropolis proposals: 4 (N <= 4) or 2 (N <= 8) configurations per wave
-    if (ka.proposal && ka.ecache && !ka.value_only && !ka.orb && !ka.ablate && !quad_grad_off()) {
-      k_quad_grad<T, N, A><<<dim3((nconf + QSlot<N>::NSL - 1) / QSlot<N>::NSL), dim3(64), 0, s>>>(ka);
-      return true;
-    }
-  }
-  if constexpr (N <= 8) {   // walker launches: 4 (N <= 4) or 2 (N <= 8) per wave
-    if (!ka.proposal && ka.wcache && !ka.value_only && !ka.orb && !ka.lapcache && !ka.one_wave) {
-      k_quad_grad<T, N, A, true><<<dim3((nconf + QSlot<N>::NSL - 1) / QSlot<N>::NSL), dim3(64), 0, s>>>(ka);
-      return true;
-    }
-  }
-  return false;
-}
-
-// Which kernel a walker launch reaches (ops.walker): the first row that matches, from the top.
-// The launch kind is not named, it is read off the KArgs fields.  T = the dtype; n = nconf;
-// Wp = RevWpb<T, true>, Ww = RevWpb<T, false> configurations per workgroup (both 1 for fp64);
-// NSL = QSlot<N>::NSL configurations per wave; LDS = dynamic LDS bytes.
+// The kernel of a walker launch (ops.walker): one case per row of route(kind, options)
+// (launch_route.h has the table of which kind and options reach which row).  T = the dtype;
+// n = nconf; Wp = RevWpb<T, true>, Ww = RevWpb<T, false> configurations per workgroup (both 1 for
+// fp64); NSL = QSlot<N>::NSL configurations per wave (4 for N <= 4, 2 for N <= 8: quad_small.h, from
+// the walker cache); LDS = dynamic LDS bytes.
 //
-//  #  mode      conditions                                          kernel                      grid                block  LDS
-//  1  GRAD      N <= 8, proposal, ecache, value_only, !orb          k_quad_value<T>             prop_blocks(n,NSL)  64     0
-//  2  GRAD      N <= 8, proposal, ecache, !value_only, !orb,        k_quad_grad<T>              ceil(n / NSL)       64     0
-//               !ablate, not (N > 4 and AIQMC_QUAD_GRAD=0)
-//  3  GRAD      N <= 8, !proposal, wcache, !value_only, !orb,       k_quad_grad<T, walker>      ceil(n / NSL)       64     0
-//               !lapcache, !one_wave
-//  4  LAP       --                                                  k_walker<T, MODE_LAP>       n                   64     Smem<T, N, true>
-//  5  GRAD      proposal, ecache                                    k_walker_rev<T, PROP>       prop_blocks(n, Wp)  64 Wp  Wp SmemRev<T, true>
-//  6  GRAD      fp32, walk_split, !proposal, !value_only,           k_walker_rev<float, SPL>    n                   128    SmemRev<float>
-//               not AIQMC_WALK_SPLIT=0
-//  7  GRAD      --                                                  k_walker_rev<T>             ceil(n / Ww)        64 Ww  Ww SmemRev<T>
-//  8  GRAD_FWD  --                                                  k_walker<T, MODE_GRAD>      n                   64     Smem<T, N, false>
+//  #  row         kernel                      grid                block  LDS
+//  1  QuadValue   k_quad_value<T>             prop_blocks(n,NSL)  64     0
+//  2  QuadGrad    k_quad_grad<T>              ceil(n / NSL)       64     0
+//  3  QuadWalker  k_quad_grad<T, walker>      ceil(n / NSL)       64     0
+//  4  LapFwd      k_walker<T, MODE_LAP>       n                   64     Smem<T, N, true>
+//  5  RevProp     k_walker_rev<T, PROP>       prop_blocks(n, Wp)  64 Wp  Wp SmemRev<T, true>
+//  6  RevSplit    k_walker_rev<float, SPL>    n                   128    SmemRev<float>
+//  7  Rev         k_walker_rev<T>             ceil(n / Ww)        64 Ww  Ww SmemRev<T>
+//  8  GradFwd     k_walker<T, MODE_GRAD>      n                   64     Smem<T, N, false>
 //
-// So proposals without an ecache (proposal reuse off) and value_only / orb walker launches take row
-// 7.  Row 6 is instantiated for float alone; every other row for both dtypes.
+// Rows 1-3 are instantiated for N <= 8 alone and row 6 for float alone (route returns them for
+// nothing else); every other row for every shape and both dtypes.
 template <typename T, int N, int A>
-static void walker_launch(int mode, const KArgs& ka, int nconf, hipStream_t s) {
-  if (mode == MODE_GRAD && quad_small<T, N, A>(ka, nconf, s)) return;
-  if (mode == MODE_LAP) {
-    k_walker<T, N, A, MODE_LAP><<<dim3(nconf), dim3(64), Smem<T, N, true>::bytes, s>>>(ka);
-  } else if (mode == MODE_GRAD && ka.proposal && ka.ecache) {   // proposals from the walker cache
-    constexpr int W = RevWpb<T, true>::value;
-    k_walker_rev<T, N, A, false, true><<<dim3(prop_blocks(nconf, W)), dim3(64 * W),
-                                        W * SmemRev<T, N, A, true>::bytes, s>>>(ka);
-  } else if (mode == MODE_GRAD) {
-    if constexpr (sizeof(T) == 4) {   // two waves per walker: an fp32 instantiation only
-      if (ka.walk_split && !ka.proposal && !ka.value_only && walk_split_on()) {
+static void walker_launch(const WalkerCall& w, int nconf, hipStream_t s) {
+  const KArgs& ka = w.ka;
+  switch (route(w.kind, sizeof(T) == 4, N, w.opts)) {
+    case Row::QuadValue:
+      if constexpr (N <= 8) k_quad_value<T, N, A><<<dim3(prop_blocks(nconf, QSlot<N>::NSL)), dim3(64), 0, s>>>(ka);
+      break;
+    case Row::QuadGrad:
+      if constexpr (N <= 8) k_quad_grad<T, N, A><<<dim3((nconf + QSlot<N>::NSL - 1) / QSlot<N>::NSL), dim3(64), 0, s>>>(ka);
+      break;
+    case Row::QuadWalker:
+      if constexpr (N <= 8)
+        k_quad_grad<T, N, A, true><<<dim3((nconf + QSlot<N>::NSL - 1) / QSlot<N>::NSL), dim3(64), 0, s>>>(ka);
+      break;
+    case Row::LapFwd:
+      k_walker<T, N, A, MODE_LAP><<<dim3(nconf), dim3(64), Smem<T, N, true>::bytes, s>>>(ka);
+      break;
+    case Row::RevProp: {   // proposals from the walker cache
+      constexpr int W = RevWpb<T, true>::value;
+      k_walker_rev<T, N, A, false, true><<<dim3(prop_blocks(nconf, W)), dim3(64 * W),
+                                          W * SmemRev<T, N, A, true>::bytes, s>>>(ka);
+      break;
+    }
+    case Row::RevSplit:   // two waves per walker: an fp32 instantiation only
+      if constexpr (sizeof(T) == 4)
         k_walker_rev<T, N, A, false, false, false, true><<<dim3(nconf), dim3(128), SmemRev<T, N, A>::bytes, s>>>(ka);
-        return;
-      }
+      break;
+    case Row::Rev: {
+      constexpr int W = RevWpb<T, false>::value;
+      static_assert(sizeof(T) == 4 || W == 1, "fp64 walker launches: one walker per workgroup, grid = nconf");
+      k_walker_rev<T, N, A><<<dim3((nconf + W - 1) / W), dim3(64 * W), W * SmemRev<T, N, A>::bytes, s>>>(ka);
+      break;
     }
-    constexpr int W = RevWpb<T, false>::value;
-    static_assert(sizeof(T) == 4 || W == 1, "fp64 walker launches: one walker per workgroup, grid = nconf");
-    k_walker_rev<T, N, A><<<dim3((nconf + W - 1) / W), dim3(64 * W), W * SmemRev<T, N, A>::bytes, s>>>(ka);
-  } else {
-    k_walker<T, N, A, MODE_GRAD><<<dim3(nconf), dim3(64), Smem<T, N, false>::bytes, s>>>(ka);
+    case Row::GradFwd:
+      k_walker<T, N, A, MODE_GRAD><<<dim3(nconf), dim3(64), Smem<T, N, false>::bytes, s>>>(ka);
+      break;
   }
 }
 template <int N, int A>
-static void walker_impl(int dtype, int mode, const KArgs& ka, int nconf, hipStream_t s) {
-  by_dtype(dtype, [&](auto t) { walker_launch<decltype(t), N, A>(mode, ka, nconf, s); });
+static void walker_impl(int dtype, const WalkerCall& w, int nconf, hipStream_t s) {
+  by_dtype(dtype, [&](auto t) { walker_launch<decltype(t), N, A>(w, nconf, s); });
 }
 
 // Local energy: adjoint pass (k_walker_rev<PREP>) then first-derivative pass (k_walker_lap).

@@ -293,11 +293,11 @@ struct KArgs {
   // this walker's pivot record of the previous sweep; the Gauss-Jordan re-uses that order (the
   // pivoted elimination only if a pivot comes out small)
   int pvok;
-  // walker launches of N <= 8 on k_walker_rev (one wave per walker) instead of the packed
-  // k_quad_grad (aiqmc_debug_set_packed_walkers; A/B and parity)
-  int one_wave;
-  // walker launch of a small batch as two waves per walker (k_walker_rev<..., SPL>: F1 and F2 at once)
-  int walk_split;
+  // reserved: no kernel reads these two ints and the host leaves them 0 (they held host-side routing
+  // switches, now LaunchOpts of launch_route.h).  They keep the offsets of the fields below, which
+  // api_util.h asserts; a kernel-side change may drop them.
+  int reserved0;
+  int reserved1;
   // k_quad_value: every slot takes the partial-pivoting LU, not the walker's order (aiqmc_debug_set_quad_pivoted)
   int quad_pivoted;
   // Metropolis caches (walker_rev.h WCache / ECache); nullptr outside aiqmc_mc_step

@@ -639,6 +639,21 @@ int aiqmc_debug_set_walker_pivots(aiqmc_ctx* ctx, int32_t reuse);
 int aiqmc_debug_launch_lds(int32_t nelectrons, int32_t natoms, int32_t dtype, int32_t kind, int32_t* bytes,
                            int32_t* waves);
 
+/* Diagnostics (host only, launches nothing): the kernel a walker launch of `kind` over nconf
+ * configurations reaches with this context's shape, dtype and current aiqmc_debug_set_* switches,
+ * as the row number (1..8) of the table above walker_launch in csrc/shape.hip.  kind:
+ * AIQMC_LAUNCH_* (aq::Launch of csrc/launch_route.h, which holds the routing); nconf matters to
+ * AIQMC_LAUNCH_SWEEP_WALKER alone (small fp32 batches run two waves per walker). */
+#define AIQMC_LAUNCH_WALKER_VALUE 0     /* aiqmc_logpsi, the observables' and the ECP quadrature's walker launch */
+#define AIQMC_LAUNCH_WALKER_ORBITALS 1  /* aiqmc_orbitals */
+#define AIQMC_LAUNCH_WALKER_GRAD 2      /* aiqmc_logpsi_grad, the DMC drift-diffusion's post-move gradient */
+#define AIQMC_LAUNCH_SWEEP_WALKER 3     /* the walker launch of a Metropolis sweep */
+#define AIQMC_LAUNCH_PROPOSAL 4         /* the proposal launch of a Metropolis sweep */
+#define AIQMC_LAUNCH_QUADRATURE 5       /* the ECP quadrature's value launch */
+#define AIQMC_LAUNCH_LAP_FORWARD 6      /* aiqmc_debug_local_energy_forward */
+#define AIQMC_LAUNCH_GRAD_FORWARD 7     /* aiqmc_debug_logpsi_grad_forward */
+int aiqmc_debug_launch_row(aiqmc_ctx* ctx, int32_t kind, int32_t nconf, int32_t* row);
+
 /* Diagnostics: walker launches of systems with N <= 8 electrons run several walkers per wave
  * (default, on = 1: four for N <= 4, two for N <= 8); on = 0 runs one wave per walker.
  * Results agree to rounding. */

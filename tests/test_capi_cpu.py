@@ -119,21 +119,35 @@ def test_product_flatten_matches_canonical_order(name):
     np.testing.assert_array_equal(nn.flatten_params(p1), system.flatten_params(p1))
 
 
-def test_param_map_host_check(tmp_path):
-    """csrc/param_map.h, the one statement of the canonical <-> kernel-layout parameter map:
-    tests/host/param_map_check.cpp (count, coverage, gmap, W_y codes, padding, lane-order copies, H2
-    values by hand) built with the Makefile's host compiler under ASan + UBSan, and run."""
+def _host_check(tmp_path, name):
+    """tests/host/<name>.cpp, a stand-alone check of a HIP-free csrc header: built with the
+    Makefile's host compiler under ASan + UBSan, run, and "<name>: 0 failures" expected."""
     import subprocess
     from aiqmc import _lib
     csrc = os.path.join(os.path.dirname(_lib.__file__), "..", "csrc")
     hipcc = re.search(r"^HIPCC\s*\?=\s*(\S+)", open(os.path.join(csrc, "Makefile")).read(), re.M).group(1)
-    exe = str(tmp_path / "param_map_check")
+    exe = str(tmp_path / name)
     subprocess.run([os.environ.get("HIPCC", hipcc), "-x", "c++", "-std=c++17", "-O1", "-g", "-Wall", "-Werror",
                     "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", f"-I{csrc}",
-                    os.path.join(ROOT, "tests", "host", "param_map_check.cpp"), "-o", exe], check=True)
+                    os.path.join(ROOT, "tests", "host", name + ".cpp"), "-o", exe], check=True)
     r = subprocess.run([exe], capture_output=True, text=True)
-    assert r.returncode == 0 and "param_map_check: 0 failures" in r.stdout, r.stdout + r.stderr
+    assert r.returncode == 0 and f"{name}: 0 failures" in r.stdout, r.stdout + r.stderr
     assert "runtime error" not in r.stderr and "Sanitizer" not in r.stderr, r.stderr
+
+
+def test_param_map_host_check(tmp_path):
+    """csrc/param_map.h, the one statement of the canonical <-> kernel-layout parameter map:
+    tests/host/param_map_check.cpp (count, coverage, gmap, W_y codes, padding, lane-order copies, H2
+    values by hand) built with the Makefile's host compiler under ASan + UBSan, and run."""
+    _host_check(tmp_path, "param_map_check")
+
+
+def test_launch_route_host_check(tmp_path):
+    """csrc/launch_route.h, which kernel a walker launch reaches: tests/host/launch_route_check.cpp
+    (every kind, N = 2..16, both dtypes and every combination of the options against the first-match
+    predicate over KArgs fields that route() replaced; every row reached; the packed rows for
+    N <= 8 alone) built and run the same way."""
+    _host_check(tmp_path, "launch_route_check")
 
 
 def test_local_energy_rejects_foreign_wavefunction():

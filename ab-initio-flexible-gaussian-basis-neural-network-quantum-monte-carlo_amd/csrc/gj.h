@@ -6,6 +6,7 @@
 // row with the first maximal |re|+|im| in column k (LAPACK izamax rule), the
 // same rows LU partial pivoting selects.  Layout and step: see gj_inverse.
 #pragma once
+#include <utility>
 #include "jets.h"
 
 namespace aq {
@@ -34,6 +35,48 @@ template <typename T> __device__ __forceinline__ T row_bcast(T x, int k) {
     case 14: return dpp<0x15E>(x);
     default: return dpp<0x15F>(x);
   }
+}
+
+// v_writelane: lane L of x <- the wave-uniform s (no builtin in this compiler)
+template <int L> __device__ __forceinline__ float wrlane(float s, float x) {
+  asm("v_writelane_b32 %0, %1, %2" : "+v"(x) : "s"(s), "n"(L));
+  return x;
+}
+template <int L> __device__ __forceinline__ double wrlane(double s, double x) {
+  const unsigned long long sb = __builtin_bit_cast(unsigned long long, s), xb = __builtin_bit_cast(unsigned long long, x);
+  unsigned lo = (unsigned)xb, hi = (unsigned)(xb >> 32);
+  asm("v_writelane_b32 %0, %1, %2" : "+v"(lo) : "s"((unsigned)sb), "n"(L));
+  asm("v_writelane_b32 %0, %1, %2" : "+v"(hi) : "s"((unsigned)(sb >> 32)), "n"(L));
+  return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
+}
+
+// f(integral_constant<int, K>) for K = 0 .. n-1: a loop whose index is a constant expression in
+// its body (an instruction's immediate operand)
+template <typename F, int... K> __device__ __forceinline__ void static_for(F&& f, std::integer_sequence<int, K...>) {
+  (f(std::integral_constant<int, K>{}), ...);
+}
+
+// One row's update of an elimination step, [re, im] += fr [mr, -qi] + fi [qi, mr], from the one
+// register pair mq = (mr, qi): the negation and the swap are v_pk_fma_f32's neg_hi / op_sel
+// modifiers (the compiler forms [mr, -qi] and [qi, mr] as two pairs: a v_xor and a v_mov per
+// step).  Same products and sums in the same order as the fp64 form.
+__device__ __forceinline__ f32x2 gj_row_update(float fr, float fi, f32x2 mq, f32x2 a) {
+  // the multiplicand is read from the low half of its pair for both results (op_sel 0 and
+  // op_sel_hi 0 on src0), which alone makes the unset high halves harmless (a splat would cost a
+  // v_mov each): change src0's modifiers and frp / fip must become splats.
+  // The compiler does not look inside the asm for hazards: its operands here are DPP moves, selects
+  // and the previous packed FMA -- never hand it the result of a transcendental (v_rcp, v_sqrt)
+  // directly, which needs a wait state before a non-transcendental reader on gfx950.
+  f32x2 frp, fip, n;
+  frp.x = fr;
+  fip.x = fi;
+  asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel_hi:[0,1,1] neg_hi:[0,1,0]" : "=v"(n) : "v"(frp), "v"(mq), "v"(a));
+  asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,1,0] op_sel_hi:[0,0,1]" : "=v"(a) : "v"(fip), "v"(mq), "v"(n));
+  return a;
+}
+__device__ __forceinline__ D2 gj_row_update(double fr, double fi, D2 mq, D2 a) {
+  a = pair_fma<double>(fr, D2{mq.x, -mq.y}, a);
+  return pair_fma<double>(fi, D2{mq.y, mq.x}, a);
 }
 
 // A[r][c] = Ph[r][c] * Yv[r][c]  (Ph complex interleaved [N][N][2], Yv real [N][N]).
@@ -229,16 +272,16 @@ __device__ __forceinline__ void gj_fixed_regs(typename Pair<T>::type* a2, T* Bou
   T zr = T(1), zi = T(0);
   bool small = false;
   T pkr = T(1), pki = T(0);
-#pragma unroll
-  for (int k = 0; k < N; ++k) {
+  auto step = [&](auto kc) {
+    constexpr int k = decltype(kc)::value;
     const int g = k / RW, ts = k % RW;
     const T pr = rdlane(pair_re<T>(a2[ts]), 16 * g + k);
     const T pim = rdlane(pair_im<T>(a2[ts]), 16 * g + k);
     const T den = pr * pr + pim * pim;
-    if (lane == k) {   // pivot k parked in lane k; the relative product is formed after the loop
-      pkr = pr;
-      pki = pim;
-    }
+    // pivot k parked in lane k (the relative product is formed after the loop): pr, pim are
+    // wave-uniform, so v_writelane
+    pkr = wrlane<k>(pr, pkr);
+    pki = wrlane<k>(pim, pki);
     // 1 / pivot by the plain formula: a |pivot|^2 outside the float range (a far-out electron's
     // row) is caught after the loop from the parked pivots and sent to the pivoted fallback, which
     // scales it (pivot_recip_me); no range branch in this loop (it cost 3 VGPRs and 15 spills in
@@ -251,19 +294,18 @@ __device__ __forceinline__ void gj_fixed_regs(typename Pair<T>::type* a2, T* Bou
     const T qi = ck ? ii : q0r * ii + q0i * ir;
     // a[r][c] <- a[r][c] + a[r][k] m with m = -q[c] (c != k) or -q[k] - 1 (c == k: there
     // a[r][k] is the lane's own entry and the result is -a[r][k] / pivot):
-    //   [re, im] += fr [mr, mi] + fi [-mi, mr]
-    const T mr = ck ? -qr - T(1) : -qr, mi = -qi;
-    const V2 m1 = pair_make<T>(mr, mi), m2 = pair_make<T>(-mi, mr);
+    //   [re, im] += fr [mr, mi] + fi [-mi, mr],  mi = -qi  (gj_row_update, from the pair (mr, qi))
+    const T mr = ck ? -qr - T(1) : -qr;
+    const V2 mq = pair_make<T>(mr, qi);
 #pragma unroll
     for (int t = 0; t < RW; ++t) {
       const T fr = row_bcast(pair_re<T>(a2[t]), k);
       const T fi = row_bcast(pair_im<T>(a2[t]), k);
-      V2 n = pair_fma<T>(fr, m1, a2[t]);
-      n = pair_fma<T>(fi, m2, n);
-      a2[t] = n;
+      a2[t] = gj_row_update(fr, fi, mq, a2[t]);
     }
     if (rg == g) a2[ts] = pair_make<T>(qr, qi);
-  }
+  };
+  static_for(step, std::make_integer_sequence<int, N>{});
   {
     // z = prod_k pivot_k / |walker pivot_k| over lanes 0..N-1 of row 0 (row_ror tree)
     const bool pl = lane < N;

@@ -393,12 +393,20 @@ __global__ __launch_bounds__(64 * MOVED_WPB) void k_moved_electron(KArgs ka) {
   ElecOut<T, A> eo;
   electron_stage<T, N, A>(P, xp, i, lc, eo);
   T* E = eb + s * RS;
+  // the wy weights row by row: NYW batches of N contiguous scalar loads, each waited for once
+  // (column by column every column waits for its own NYW strided loads); every column's sum
+  // keeps its order
+  PJ<T> sy[N];
+#pragma unroll
+  for (int col = 0; col < N; ++col) sy[col] = P[Ly::wy + col] * eo.yst[0];
+#pragma unroll
+  for (int m = 1; m < NYW; ++m) {
+#pragma unroll
+    for (int col = 0; col < N; ++col) sy[col] = sy[col] + P[Ly::wy + m * N + col] * eo.yst[m];
+  }
 #pragma unroll
   for (int col = 0; col < N; ++col) {
-    PJ<T> sy = P[Ly::wy + col] * eo.yst[0];
-#pragma unroll
-    for (int m = 1; m < NYW; ++m) sy = sy + P[Ly::wy + m * N + col] * eo.yst[m];
-    const PJ<T> yt = eo.env * sy;
+    const PJ<T> yt = eo.env * sy[col];
     if (lc == 3) E[EC::yv + col] = yt.v;
     else E[EC::yd + lc * N + col] = yt.d1;
   }

@@ -1,9 +1,7 @@
-// api_util.h -- what every translation unit of the library shares (the context units aiqmc.hip,
-// dmc.hip, debug.hip, observables.hip, components.hip, density.hip and corrsamples.hip, the
-// context-free loss.hip, sr_gram.hip and blocking.hip, and shape.hip): the error return, the HIP
-// error check and the prologue of the entry points that take a context and a batch of positions,
-// and the typed launch layer (by_dtype, the grid helper and the KArgs builders).  What only the
-// context units call of one another is declared in host_shared.h.
+// api_util.h -- what every translation unit of the library shares (ctx.h lists them): the error
+// return, the HIP error check and the prologue of the entry points that take a context and a batch
+// of positions, and the typed launch layer (by_dtype, the grid helper and the KArgs builders).
+// What only the context units call of one another is declared in host_shared.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -64,17 +62,9 @@ inline auto by_dtype(int dtype, F&& f) {
 // grid of n threads in workgroups of `per`
 inline dim3 blocks(int64_t n, int per) { return dim3((unsigned)((n + per - 1) / per)); }
 
-// The layout the kernels were compiled against: KArgs keeps its size and the offsets of what follows
-// its reserved pair (walker_kernel.h) until a kernel-side change moves them on purpose.
-static_assert(sizeof(KArgs) == 368 && offsetof(KArgs, reserved0) == 284 && offsetof(KArgs, reserved1) == 288 &&
-                  offsetof(KArgs, quad_pivoted) == 292 && offsetof(KArgs, wcache) == 296 && offsetof(KArgs, ecache) == 304 &&
-                  offsetof(KArgs, lapcache) == 312 && offsetof(KArgs, logabs) == 320 && offsetof(KArgs, phase) == 328 &&
-                  offsetof(KArgs, grad) == 336 && offsetof(KArgs, el) == 344 && offsetof(KArgs, sumsq) == 352 &&
-                  offsetof(KArgs, gown) == 360,
-              "KArgs layout changed");
-
 // ---- KArgs builders: what every launch of a kind shares; the call site adds its outputs
-// the context's part of every launch
+// the context's part of every launch (the memset relies on an all-zero-bytes KArgs being the
+// value-initialised one, which tests/host/launch_abi_check.cpp checks)
 inline KArgs base_args(const aiqmc_ctx* c) {
   KArgs ka;
   std::memset(&ka, 0, sizeof(ka));

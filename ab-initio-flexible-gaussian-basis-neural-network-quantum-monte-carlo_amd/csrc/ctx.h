@@ -1,6 +1,21 @@
-// ctx.h -- host-side context + per-shape dispatch table shared by every C-ABI translation unit that
-// takes a context (aiqmc.hip, dmc.hip, debug.hip, observables.hip, components.hip, density.hip,
-// corrsamples.hip, rdm.hip) and the per-shape kernel TUs (shape.hip); api_util.h includes it.
+// ctx.h -- host-side context + per-shape dispatch table.  It includes the launch ABI (kargs.h) and
+// no header with a kernel or device function in it, so a unit sees the kernels it includes itself
+// and no others.  Of the kernels' side it brings layout.h alone (through param_map.h: the offsets
+// of Lay<N,A>, plain constants that the parameter map walks), so a layout change still rebuilds
+// every unit.
+//
+// Who includes what (the one list; api_util.h, host_shared.h and the Makefile point here):
+//   api_util.h (which includes this file, and with it devbuf.h, kargs.h, launch_route.h,
+//   param_map.h and layout.h): every unit
+//     with a context     aiqmc, dmc, debug, observables, rdm, components, density, corrsamples
+//     context-free       loss, sr_gram, blocking
+//     per shape          shape.hip
+//   host_shared.h        aiqmc, dmc, debug, observables, rdm (it brings ecp_args.h)
+//   reduce.h             aiqmc, dmc, loss, corrsamples
+//   kernel headers       jets.h: aiqmc, observables, rdm (and dmc through ecp.h); limdrift.h: aiqmc,
+//                        debug; ecp.h: aiqmc, dmc; walker_fwd.h, walker_rev.h, walker_lap.h,
+//                        walker_pgrad.h, quad_small.h (with gj.h, electron.h): shape.hip alone
+//   none of them         components, density, corrsamples, loss, sr_gram, blocking
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -11,9 +26,9 @@
 
 #include "aiqmc.h"
 #include "devbuf.h"
+#include "kargs.h"
 #include "launch_route.h"
 #include "param_map.h"
-#include "walker_kernel.h"
 
 using aq::KArgs;
 // aiqmc_profile_read's slots: the launches that timed() brackets (the numbers are the C-ABI's)

@@ -10,6 +10,7 @@
 
 #include "aiqmc.h"
 #include "host_shared.h"
+#include "limdrift.h"
 
 using namespace aq;
 using namespace aq_host;

@@ -16,6 +16,7 @@
 // Reference quirks (oracle/pphamiltonian.py E1-E7) are reproduced; the ECP arithmetic itself is
 // done in double for both dtypes (it is < 1% of the launch time).
 #pragma once
+#include "ecp_args.h"
 #include "jets.h"
 
 namespace aq {
@@ -68,33 +69,6 @@ __device__ __forceinline__ void ecp_rotate(const T* R, const double p[3], double
 #pragma unroll
   for (int l = 0; l < 3; ++l) out[l] = p[0] * (double)R[l] + p[1] * (double)R[3 + l] + p[2] * (double)R[6 + l];
 }
-
-// Device tables (double): atoms [A][3], charges [A], then per atom KL local triplets
-// (n, coefficient, exponent) and L*KN nonlocal triplets.
-struct EcpArgs {
-  int B, N, A, KL, KN, L;
-  const double* tab;
-  const void* pos;      // [B][3N]
-  const void* rot;      // [B][9]
-  const void* lp0;      // [B] log|psi| at the walker
-  const void* ph0;      // [B] phase at the walker
-  const void* lpq;      // [B][N][A][50] log|psi| at the quadrature configurations
-  const void* phq;      // [B][N][A][50] phase
-  const void* eall;     // [B] all-electron local energy (V_ee + V_en + V_nn + KE)
-  void* e_re;           // [B] outputs
-  void* e_im;
-  void* xnew;           // k_ecp_points output [B*N*A*50][3]
-  uint64_t seed, step;  // k_ecp_rot
-  int skip_nl;          // k_ecp_energy: nonlocal coefficients all zero -- no quadrature was run
-  int cdf_lds;          // k_tmove: dynamic LDS holds every electron's cdf row [N][A*50+1][2]
-  // T-moves (k_tmove)
-  double tstep;
-  const void* usel;     // [B] selection uniform (NULL: Philox)
-  const void* uacc;     // [B][N] acceptance uniforms (NULL: Philox)
-  void* acc;            // [B][N] acceptance out (optional)
-  void* pos_out;        // [B][3N] positions, updated in place
-  double* scr;          // [B][N*A*50][4] forward amplitude (re, im), ratio (re, im)
-};
 
 // Uniform Haar O(3): a uniformly random unit quaternion (4 normals, normalised) gives SO(3);
 // an independent fair sign makes it O(3), the support of jax.random.orthogonal.

@@ -1,12 +1,9 @@
-// host_shared.h -- the host helpers that more than one context translation unit calls (aiqmc.hip,
-// dmc.hip, debug.hip, observables.hip, rdm.hip).  Each is defined in the unit named beside it; none is exported (hidden
-// visibility: the library's dynamic symbol table is the C-ABI of include/aiqmc.h).
+// host_shared.h -- the host helpers that more than one context translation unit calls (the units
+// that include it are listed in ctx.h).  Each is defined in the unit named beside it; none is
+// exported (hidden visibility: the library's dynamic symbol table is the C-ABI of include/aiqmc.h).
 #pragma once
 #include "api_util.h"
-
-namespace aq {
-struct EcpArgs;   // ecp.h
-}
+#include "ecp_args.h"
 
 namespace aq_host {
 #pragma GCC visibility push(hidden)
@@ -28,8 +25,8 @@ struct SweepArgs {
   // inter-kernel gap fewer per sweep; same arithmetic, accept_one); a set *pending is applied first
   aq::AccArgs* pending = nullptr;
   bool defer = false;
-  // fp32 mc_step: this sweep's zeroed pair of fused limdrift accumulators (walker_kernel.h
-  // TACC_SCALE; the two k_taueff launches are then skipped), or its k_taueff_part partial sums
+  // fp32 mc_step: this sweep's zeroed pair of fused limdrift accumulators (kargs.h
+  // TACC_STRIDE; the two k_taueff launches are then skipped), or its k_taueff_part partial sums
   unsigned long long* tacc = nullptr;
   unsigned long long* tpart = nullptr;
   bool pvok = false;             // the walker cache holds the previous sweep's pivot order

@@ -27,6 +27,7 @@
 
 #include "aiqmc.h"
 #include "host_shared.h"
+#include "jets.h"
 
 using namespace aq;
 

@@ -24,6 +24,8 @@
 // the walker launches -- see its own header below.
 // log|psi| = log|det| + J_ae + J_ee (the Jastrows multiply the matrix, nn.py:504, Q11).
 #pragma once
+#include "kargs.h"
+#include "limdrift.h"
 #include "walker_rev.h"
 
 namespace aq {

@@ -34,6 +34,7 @@
 
 #include "aiqmc.h"
 #include "host_shared.h"
+#include "jets.h"
 
 using namespace aq;
 

@@ -6,6 +6,9 @@
 #include <cstring>
 
 #include "api_util.h"
+// the wavefront kernels; walker_fwd.h first keeps the order their definitions have had in the code object
+#include "walker_fwd.h"
+#include "limdrift.h"
 #include "walker_lap.h"
 #include "quad_small.h"
 #include "walker_pgrad.h"

@@ -15,9 +15,9 @@
 //        sum_m abar_m phi''(z_m) |grad z_m|^2  +  sum_leaves abar_leaf lap(leaf)
 //    (leaves: the ae features, the pair terms of the column means g2).  Each direction
 //    lane adds abar_m phi''(z_m) (dz_m/dx_{e,c})^2 per node; no lane carries second
-//    derivatives through the dense stream (the forward-Laplacian kernel walker_kernel.h
+//    derivatives through the dense stream (the forward-Laplacian kernel walker_fwd.h
 //    does, with twice the per-lane state and one wave per SIMD).  The determinant's own
-//    second-order terms use its low-rank structure (walker_kernel.h header):
+//    second-order terms use its low-rank structure (walker_fwd.h header):
 //        Re[(2 dPhi_e.Yt' + Phi_e.Yt'') b_e - sum_{r,s} S_rs S_sr - 2 sum_r z_r S_re - (w.b_e)^2]
 //    with S = sum_f diag(U_f) Q_f, U = dH/dx_{e,c}, w = Phi[e,:] dYt[e,:], z = B^T w.  The
 //    Jastrow factors and the per-electron stage (envelope, Ylm stream, ae features) are
@@ -26,7 +26,7 @@
 #include "electron.h"
 #include "jets.h"
 #include "layout.h"
-#include "walker_kernel.h"
+#include "kargs.h"
 #include "walker_rev.h"
 
 namespace aq {

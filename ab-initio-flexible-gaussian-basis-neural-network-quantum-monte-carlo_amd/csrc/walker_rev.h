@@ -19,7 +19,8 @@
 #pragma once
 #include "jets.h"
 #include "layout.h"
-#include "walker_kernel.h"
+#include "kargs.h"
+#include "limdrift.h"
 #include "gj.h"
 #include "electron.h"
 

@@ -150,6 +150,15 @@ def test_launch_route_host_check(tmp_path):
     _host_check(tmp_path, "launch_route_check")
 
 
+def test_launch_abi_host_check(tmp_path):
+    """csrc/kargs.h, ecp_args.h and launch_route.h, what the host and the kernels share:
+    tests/host/launch_abi_check.cpp (the headers compile without HIP; sizeof and every field offset
+    of KArgs, AccArgs and EcpArgs against the frozen table; value-initialised KArgs / AccArgs are
+    all-zero bytes, as base_args' memset assumes; the accumulator word constants) built and run the
+    same way."""
+    _host_check(tmp_path, "launch_abi_check")
+
+
 def test_local_energy_rejects_foreign_wavefunction():
     from aiqmc.Energy import hamiltonian
     with pytest.raises(TypeError):

@@ -250,7 +250,7 @@ def test_metropolis_sweep_fp32(sweep, name):
     """(e) fp32 against the fp64 kernels from the same float32-rounded start and host draws:
     everything finite, the accept count within max(1, B N / 100) of the fp64 count, walkers that
     took the same decisions within 1e-4; the fused and unfused limdrift reductions bitwise equal
-    (|grad|^2 reaches 1e9 here: the mid word of the integer accumulators, walker_kernel.h)."""
+    (|grad|^2 reaches 1e9 here: the mid word of the integer accumulators, limdrift.h)."""
     s, g, c64 = _ctx(name, torch.float64)
     _, _, c32 = _ctx(name, torch.float32)
     _, x64, m64, _ = _sweep(c64, g, sweep, torch.float64, True)

@@ -346,7 +346,7 @@ def test_small_n_packed_walkers_match_one_wave_path(name, dtype):
 @pytest.mark.parametrize("name", ["N2", "Be"])
 def test_fused_limdrift_reduction_matches_reduction_launches(name):
     """fp32 mc_step sums the two limdrift reductions of a sweep (VMCmcstep.py:11-14) inside the
-    walker and proposal launches as exact integer accumulations (walker_kernel.h TACC_SCALE)
+    walker and proposal launches as exact integer accumulations (kargs.h TACC_SCALE, limdrift.h)
     instead of two reduction launches.  The integer sum is order independent: repeated runs are
     bitwise equal, and so is the unfused path, whose reduction launches (k_taueff_part) sum the
     same integers.  Against the fp64 tree-sum launch (k_taueff, mode 3) the limdrift factor

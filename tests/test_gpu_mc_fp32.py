@@ -1,7 +1,7 @@
 """The benched fp32 Metropolis path against the oracle (VERDICT r3 "Next" #1 and #6).
 
 1. The fp32 limdrift reduction (VMCmcstep.py:11-14, quirk Q8).  mc_step sums every
-   configuration's |grad|^2 as exact integers (walker_kernel.h `tacc_split`: lo / mid / hi words
+   configuration's |grad|^2 as exact integers (limdrift.h `tacc_split`: lo / mid / hi words
    and a bad count), either fused into the walker / proposal launches (mode 0) or in
    k_taueff_part's partials (mode 1); mode 2 is the fp64 tree sum (k_taueff).  Vectors with
    1e15 (above the round-3 2^48 fixed-point cap), 1e30, 3e38, a float-overflowing pair, +inf

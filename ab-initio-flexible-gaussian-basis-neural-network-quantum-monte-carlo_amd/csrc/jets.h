@@ -35,6 +35,53 @@ template <typename T> __device__ __forceinline__ cptr<T> param_ptr(const void* p
   return (cptr<T>)(const __attribute__((address_space(4))) void*)p;
 }
 
+// Addressing vocabulary of the per-lane (vector-memory) accesses: a wave-uniform base pointer plus an
+// unsigned 32-bit element offset, uat(base, off)[c] with a compile-time c.  The byte offset is formed
+// in 32 bits and zero-extended, which is the shape the backend selects into the scalar-base form of
+// global_load / global_store / global_load_lds (SGPR-pair base, one 32-bit VGPR offset, 13-bit
+// immediate): no 64-bit VALU address arithmetic and one offset register per access family instead of
+// a VGPR pair per pointer.  `base[int]` sign-extends the index and shifts it in 64 bits, which the
+// selector cannot prove equal to a 32-bit offset, so it builds a per-lane 64-bit pointer.
+// Contract: base is wave-uniform for the compiler (kernel arguments, readfirstlane'd indices, scalar
+// 64-bit arithmetic such as conf * size) and off * sizeof(T) plus the constant part stays below 2^32
+// -- the offset within ONE record or the parameter block, never a whole-batch product (the kernels
+// static_assert their record sizes).
+// The byte offset passes through an empty asm (a VGPR the optimiser cannot look into): left visible,
+// a clamp or select in the offset is hoisted over the zero-extension (zext(min(l, c)) becomes a
+// 64-bit select) and the access falls back to a VGPR-pair address.
+__device__ __forceinline__ size_t ubytes(unsigned off, unsigned elem) {
+  unsigned b = off * elem;
+  asm("" : "+v"(b));
+  return (size_t)b;
+}
+template <typename T> __device__ __forceinline__ cptr<T> uat(cptr<T> base, unsigned off) {
+  typedef const __attribute__((address_space(4))) char* B;
+  return (cptr<T>)((B)base + ubytes(off, sizeof(T)));
+}
+template <typename T> __device__ __forceinline__ T* uat(T* base, unsigned off) {
+  return (T*)((char*)base + ubytes(off, sizeof(T)));
+}
+template <typename T> __device__ __forceinline__ const T* uat(const T* base, unsigned off) {
+  return (const T*)((const char*)base + ubytes(off, sizeof(T)));
+}
+// The base of an access family held in an SGPR pair, opaque to the optimiser: the constant parts of
+// the family's offsets then stay immediates of the accesses (folded into the base, a constant beyond
+// the immediate's range is added per lane in 64 bits again).
+template <typename T> __device__ __forceinline__ cptr<T> ubase(cptr<T> p) {
+  asm volatile("" : "+s"(p));
+  return p;
+}
+// (a generic pointer passes as a global one, so that its accesses stay global_* instead of flat_*)
+template <typename T> __device__ __forceinline__ T* ubase(T* p) {
+  auto g = (__attribute__((address_space(1))) T*)p;
+  asm volatile("" : "+s"(g));
+  return (T*)g;
+}
+// every record the kernels index with uat() (bytes of its widest element type)
+template <int ELEMS> struct URecordFits {
+  static constexpr bool value = (long long)ELEMS * 8 < (1ll << 28);
+};
+
 // Scalar math.  float uses the hardware approximations (v_sqrt_f32, v_rcp_f32,
 // v_exp_f32: ~1 ulp), which is well inside the fp32 parity tolerance of the
 // reference's own float32 arithmetic; double keeps the correctly rounded

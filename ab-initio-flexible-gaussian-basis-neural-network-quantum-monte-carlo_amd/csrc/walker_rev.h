@@ -317,17 +317,29 @@ template <int N> __constant__ PairTab<N> pair_tab{};
 // n consecutive elements global -> LDS by gfx950 LDS-DMA (global_load_lds_dword: lane l of each
 // wave-instruction writes the wave-uniform LDS base + 4 l; no VGPR destination).  The data is
 // counted on vmcnt: the caller waits (s_waitcnt vmcnt(0)) before anything reads or overwrites it.
-template <typename T>
-__device__ __forceinline__ void lds_dma(T* dst, const T* src, int n, int lane) {
-  const int nw = n * (int)sizeof(T) / 4;
-  const float* s = (const float*)src;
-  float* d = (float*)dst;
-#pragma unroll
-  for (int w = 0; w < nw; w += 64) {
-    if (w + lane < nw)
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(s + w + lane),
-                                       (__attribute__((address_space(3))) void*)(d + w), 4, 0, 0);
+// src is wave-uniform and pinned to an SGPR pair (ubase): every instruction is src + the lane (uat,
+// jets.h) with its 64-lane block W as the instruction's immediate offset, which the hardware adds
+// to the global and the LDS address alike.  The partial last block forms its lane offset inside its
+// branch: instruction selection works a basic block at a time and takes an offset zero-extended in
+// another block for a 64-bit one.
+template <int NW, int W = 0>
+__device__ __forceinline__ void lds_dma_blocks(__attribute__((address_space(3))) void* d, const float* s, int lane) {
+  typedef const __attribute__((address_space(1))) void* G;
+  if constexpr (W < NW) {
+    static_assert(W * 4 < 4096, "block offset beyond the immediate");
+    if constexpr (W + 64 <= NW) {
+      __builtin_amdgcn_global_load_lds((G)uat(s, (unsigned)lane), d, 4, W * 4, 0);
+    } else if (W + lane < NW) {
+      unsigned b = (unsigned)lane * 4u;
+      asm volatile("" : "+v"(b));
+      __builtin_amdgcn_global_load_lds((G)((const char*)s + (size_t)b), d, 4, W * 4, 0);
+    }
+    lds_dma_blocks<NW, W + 64>(d, s, lane);
   }
+}
+template <typename T, int n>
+__device__ __forceinline__ void lds_dma(T* dst, const T* src, int lane) {
+  lds_dma_blocks<n * (int)sizeof(T) / 4>((__attribute__((address_space(3))) void*)dst, (const float*)ubase(src), lane);
 }
 
 // c ? x : +0 as a bit mask (no select of a loaded value: see the F1 cache loads)
@@ -635,6 +647,11 @@ k_walker_rev(KArgs ka) {
   constexpr bool xlane = PROP;
   using SM = SmemRev<T, N, A, fwd_reg>;
   using LCc = LapCache<N, A>;
+  // the records and tables indexed by a 32-bit lane offset (uat, jets.h)
+  static_assert(URecordFits<Ly::total_ext>::value && URecordFits<WCache<N, A>::size>::value &&
+                    URecordFits<ECache<N, A>::size>::value && URecordFits<LCc::size>::value &&
+                    URecordFits<3 * N>::value && sizeof(PairTab<N>) < (1u << 28),
+                "record too large for a 32-bit lane offset");
   constexpr int D0 = SM::D0;
   constexpr int WPB = SPL ? 2 : RevWpb<T, PROP, PREP>::value;
   const cptr<T> P = param_ptr<T>(ka.prm);
@@ -724,6 +741,9 @@ k_walker_rev(KArgs ka) {
   // walker launch re-using its previous sweep's pivot order (F5; KArgs::pvok)
   const bool wfix = !PREP && !PROP && !isprop && ka.pvok != 0;
   T* Wc = (T*)ka.wcache + (size_t)(reuse ? pb : conf) * WC::size;
+  // PROP: the record's base stays one SGPR pair (left to the optimiser, the lane offset of F1's
+  // block loads is added to the buffer first and the record's offset per lane in 64 bits)
+  if constexpr (PROP) Wc = ubase(Wc);
   T* Lw = PREP ? (T*)ka.lapcache + (size_t)conf * LCc::size : nullptr;
   const T* Eq = reuse ? (const T*)ka.ecache + (size_t)conf * EC::size : nullptr;
   T* Yv = sm + SM::yv;
@@ -774,19 +794,20 @@ k_walker_rev(KArgs ka) {
   // the Jastrow parameters of pair (pi, o) of this lane (o = lane & 15, clamped)
   auto jee_params = [&](T& cusp, T& al) {
     const int os = (lane & 15) < N ? (lane & 15) : N - 1;
-    cusp = P[Ly::jee_c + pi * N + os];
-    al = P[Ly::jee_a + pi * N + os];
+    const cptr<T> row = P + pi * N;   // pi is wave-uniform: row pi of both tables
+    cusp = *uat(row + Ly::jee_c, (unsigned)os);
+    al = *uat(row + Ly::jee_a, (unsigned)os);
   };
   if (reuse) {
     // walker pb's cached stage and pair sums, electron pi's entries from k_moved_electron;
     // all loads issued before the first LDS store
     // the walker's Yt, ae-feature and g2 blocks go global -> LDS by LDS-DMA (no VGPR staging, no
     // per-element selection); the moved electron's rows are patched in after they land
-    lds_dma<T>(Yv, Wc + WC::yv, N * N, lane);
-    lds_dma<T>(sm + SM::hl, Wc + WC::h0, N * D0, lane);
-    lds_dma<T>(g2, Wc + WC::g2, 3 * 2 * N * 4, lane);
-    const T eyv = Eq[EC::yv + (lane < N ? lane : N - 1)];
-    const T eh0 = Eq[EC::h0 + (lane < D0 ? lane : D0 - 1)];
+    lds_dma<T, N * N>(Yv, Wc + WC::yv, lane);
+    lds_dma<T, N * D0>(sm + SM::hl, Wc + WC::h0, lane);
+    lds_dma<T, 3 * 2 * N * 4>(g2, Wc + WC::g2, lane);
+    const T eyv = *uat(Eq + EC::yv, (unsigned)(lane < N ? lane : N - 1));
+    const T eh0 = *uat(Eq + EC::h0, (unsigned)(lane < D0 ? lane : D0 - 1));
     // PROP: F0's positions too (walker pb's, the moved electron's proposed position from
     // k_moved_electron), so that every global load of F0/F1 is in flight before one barrier
     // Every load is issued unconditionally at a clamped, in-bounds index and the moved electron's
@@ -795,10 +816,10 @@ k_walker_rev(KArgs ka) {
     T x0 = T(0), xm = T(0), jc = T(0), ja = T(0);
     if constexpr (PROP) {
       const int l3 = lane < 3 * N ? lane : 3 * N - 1;
-      x0 = ((const T*)ka.pos)[(size_t)pb * 3 * N + l3];
-      xm = Eq[EC::xp + (mvl ? lane - 3 * pi : 0)];
+      x0 = *uat((const T*)ka.pos + (size_t)pb * 3 * N, (unsigned)l3);
+      xm = *uat(Eq + EC::xp, (unsigned)(mvl ? lane - 3 * pi : 0));
       jee_params(jc, ja);   // before the cache loads: F2's pair values wait for these only
-      rsl = rowsrc[lane < N ? lane : N - 1];   // F5's slot table (after F4)
+      rsl = *uat(rowsrc, (unsigned)(lane < N ? lane : N - 1));   // F5's slot table (after F4)
     }
     {
       // one load per value from a selected address, masked to +0 by a bit and: a select between
@@ -818,7 +839,7 @@ k_walker_rev(KArgs ka) {
         const T a2 = Wc[WC::jee];
         jve = lane == 0 ? a2 : T(0);
       }
-      pvr = Wc[WC::pv + (lane < 2 * N + 2 ? lane : 2 * N + 1)];   // to LDS after F4 (SmemRev::pv)
+      pvr = *uat(Wc + WC::pv, (unsigned)(lane < 2 * N + 2 ? lane : 2 * N + 1));   // to LDS after F4 (SmemRev::pv)
     }
     if constexpr (PROP) {
       if (mvl) sm[SM::R + (lane - 3 * pi)] = x0;             // old position of the moved electron
@@ -1055,6 +1076,7 @@ k_walker_rev(KArgs ka) {
   const bool ilive = fi < N;
   const int ic = ilive ? fi : N - 1;
   const bool inG1 = ic >= nup;
+  const unsigned xrec = (unsigned)(ic * 4 + ff);   // the lane's record of the lane-order weight blocks
   T hreg = T(0);
   // fp32 proposals with 13 <= N <= 16 (4 rows per lane in F5's register layout = the 16x16 MFMA
   // accumulator layout): Phi = h^3 W + b on the matrix cores (F5 below).  Round 4, interleaved A/B
@@ -1068,20 +1090,24 @@ k_walker_rev(KArgs ka) {
   T owm[4];   // phi_mfma: the MFMA B operand W_s[f = lane >> 4][c = lane & 15] (re, im) of both spins
   auto orb_load = [&]() {
     const int cl = (lane & 15) < N ? (lane & 15) : N - 1;
-    const cptr<T> wcol = P + 2 * cl;
+    // one base for the weights and the biases (orb_b follows orb_w), the spin and unit parts immediates
+    const cptr<T> ob = ubase(P + Ly::orb_w);
+    constexpr int OB = Ly::orb_b - Ly::orb_w;
     if constexpr (phi_mfma) {
-      const int fq = lane >> 4;
+      const cptr<T> wq = uat(ob, (unsigned)(2 * cl + (lane >> 4) * N * 2));
 #pragma unroll
       for (int s = 0; s < 2; ++s) {
-        owm[2 * s] = wcol[Ly::orb_w + (s * 4 + fq) * N * 2];
-        owm[2 * s + 1] = wcol[Ly::orb_w + (s * 4 + fq) * N * 2 + 1];
+        owm[2 * s] = wq[s * 4 * N * 2];
+        owm[2 * s + 1] = wq[s * 4 * N * 2 + 1];
       }
     } else {
+      const cptr<T> wq = uat(ob, (unsigned)(2 * cl));
 #pragma unroll
-      for (int s = 0; s < 8; ++s) ow[s] = pair_make<T>(wcol[Ly::orb_w + s * N * 2], wcol[Ly::orb_w + s * N * 2 + 1]);
+      for (int s = 0; s < 8; ++s) ow[s] = pair_make<T>(wq[s * N * 2], wq[s * N * 2 + 1]);
     }
+    const cptr<T> bq = uat(ob, (unsigned)(2 * cl));
 #pragma unroll
-    for (int s = 0; s < 2; ++s) obs[s] = pair_make<T>(wcol[Ly::orb_b + s * N * 2], wcol[Ly::orb_b + s * N * 2 + 1]);
+    for (int s = 0; s < 2; ++s) obs[s] = pair_make<T>(bq[OB + s * N * 2], bq[OB + s * N * 2 + 1]);
   };
   if (!AQ_ABL(2)) {
   // this lane's layer weights (electron ic's conv weights and biases at unit ff, the single
@@ -1098,15 +1124,19 @@ k_walker_rev(KArgs ka) {
     const cptr<T> sb = P + (l == 0 ? Ly::sng_b0 : (l == 1 ? Ly::sng_b1 : Ly::sng_b2));
     if constexpr (xlane) {
       // the lane's records of the lane-order blocks: 2 + 2 + 1 sixteen-byte loads
+      // each block from its layer-0 base (ubase) plus the lane's record; the layer is an immediate
       T cw8[Ly::XQ], sw8[Ly::XQ], cb4[Ly::XB];
+      const cptr<T> xw = uat(ubase(P + Ly::xcw(0)), xrec * Ly::XQ) + (Ly::xcw(l) - Ly::xcw(0));
+      const cptr<T> xs_ = uat(ubase(P + Ly::xsw(0)), (unsigned)ff * Ly::XQ) + (Ly::xsw(l) - Ly::xsw(0));
+      const cptr<T> xb = uat(ubase(P + Ly::xcb(0)), xrec * Ly::XB) + (Ly::xcb(l) - Ly::xcb(0));
       if (l == 0) {
-        ld_use<T, Ly::XQ, Ly::Q0>(P + Ly::xcw(l) + (ic * 4 + ff) * Ly::XQ, cw8);
-        ld_use<T, Ly::XQ, Ly::Q0>(P + Ly::xsw(l) + ff * Ly::XQ, sw8);
-        ld_use<T, Ly::XB, Ly::CBN(Ly::Q0)>(P + Ly::xcb(l) + (ic * 4 + ff) * Ly::XB, cb4);
+        ld_use<T, Ly::XQ, Ly::Q0>(xw, cw8);
+        ld_use<T, Ly::XQ, Ly::Q0>(xs_, sw8);
+        ld_use<T, Ly::XB, Ly::CBN(Ly::Q0)>(xb, cb4);
       } else {
-        ld_use<T, Ly::XQ, Ly::Q1>(P + Ly::xcw(l) + (ic * 4 + ff) * Ly::XQ, cw8);
-        ld_use<T, Ly::XQ, Ly::Q1>(P + Ly::xsw(l) + ff * Ly::XQ, sw8);
-        ld_use<T, Ly::XB, Ly::CBN(Ly::Q1)>(P + Ly::xcb(l) + (ic * 4 + ff) * Ly::XB, cb4);
+        ld_use<T, Ly::XQ, Ly::Q1>(xw, cw8);
+        ld_use<T, Ly::XQ, Ly::Q1>(xs_, sw8);
+        ld_use<T, Ly::XB, Ly::CBN(Ly::Q1)>(xb, cb4);
       }
 #pragma unroll
       for (int q = 0; q < SM::QM; ++q)
@@ -1135,7 +1165,8 @@ k_walker_rev(KArgs ka) {
     for (int q = 0; q < SM::QM; ++q)
       if (q >= 4 * (Q / 4) && q < Q) wcb[l][q] = cb[q];
     }
-    wsb[l] = sb[ff];
+    if constexpr (xlane) wsb[l] = uat(ubase(P + Ly::sng_b0), (unsigned)ff)[(l == 0 ? 0 : (l == 1 ? Ly::sng_b1 : Ly::sng_b2) - Ly::sng_b0)];
+    else wsb[l] = sb[ff];
   };
   lw_load(0);
 #pragma unroll
@@ -1438,19 +1469,20 @@ k_walker_rev(KArgs ka) {
   if (!q_mfma && lane < 4 * N && !AQ_ABL(8)) {
     const int r = lane >> 2, f = lane & 3;
     const int sp = r < nup ? 0 : 1;
+    const cptr<T> wrow = uat(ubase(P + Ly::orb_w), (unsigned)((sp * 4 + f) * N * 2));   // W_{s(r)}[f][:]
     T q = T(0), q1 = T(0);   // even / odd c: two independent chains
 #pragma unroll
     for (int c = 0; c < N; ++c) {
       const T yv = Yv[r * N + c];
-      const T wr = P[Ly::orb_w + ((sp * 4 + f) * N + c) * 2] * yv;
-      const T wi = P[Ly::orb_w + ((sp * 4 + f) * N + c) * 2 + 1] * yv;
+      const T wr = wrow[c * 2] * yv;
+      const T wi = wrow[c * 2 + 1] * yv;
       // Re Q_f[r,r] (PH: Im Q_f[r,r])
       const T qc = PH ? wr * BIM(c, r) + wi * BRE(c, r) : wr * BRE(c, r) - wi * BIM(c, r);
       if (c & 1) q1 += qc;
       else q += qc;
     }
     q += q1;
-    hbar[SM::hoff(3) + rowsrc[r] * 4 + f] = q;
+    hbar[SM::hoff(3) + *uat(rowsrc, (unsigned)r) * 4 + f] = q;
   }
   if constexpr (PREP) {
     // B, Phi and Q_f[r,s] = sum_c W_{s(r)}[f,c] Yt[r,c] B[c,s] for the determinant terms
@@ -1598,9 +1630,12 @@ k_walker_rev(KArgs ka) {
       const int QF = Q / 4;
       T cg[SM::QM];
       T bcw8[Ly::XQ];   // xlane: this lane's conv weights (electron ic, unit ff), 2 sixteen-byte loads
+      cptr<T> xr = P;   // xlane: the single-layer weight rows of the lane's unit, rows q an immediate apart
       if constexpr (xlane) {
-        if (l == 0) ld_use<T, Ly::XQ, Ly::Q0>(P + Ly::xcw(l) + (ic * 4 + ff) * Ly::XQ, bcw8);
-        else ld_use<T, Ly::XQ, Ly::Q1>(P + Ly::xcw(l) + (ic * 4 + ff) * Ly::XQ, bcw8);
+        const cptr<T> xw = uat(ubase(P + Ly::xcw(0)), xrec * Ly::XQ) + (Ly::xcw(l) - Ly::xcw(0));
+        if (l == 0) ld_use<T, Ly::XQ, Ly::Q0>(xw, bcw8);
+        else ld_use<T, Ly::XQ, Ly::Q1>(xw, bcw8);
+        xr = uat(ubase(P + Ly::xsr(0)), (unsigned)ff * 4) + (Ly::xsr(l) - Ly::xsr(0));
       }
 #pragma unroll
       for (int q = 0; q < SM::QM; ++q) {
@@ -1609,7 +1644,10 @@ k_walker_rev(KArgs ka) {
           const int qq = full ? q + ff : q;     // output this lane forms
           T cb = T(0);
           T srow[4];   // xlane: single-layer weight row qq, one sixteen-byte load
-          if constexpr (xlane) ld_vec<T, 4>(P + Ly::xsr(l) + qq * 4, srow);
+          if constexpr (xlane) {
+            if (full) ld_vec<T, 4>(xr + q * 4, srow);               // row q + ff
+            else ld_vec<T, 4>(P + Ly::xsr(l) + q * 4, srow);        // wave-uniform row
+          }
 #pragma unroll
           for (int m = 0; m < 4; ++m) {
             cb += zq[m] * (xlane ? srow[m] : sngw[qq * 4 + m]);
@@ -1853,21 +1891,22 @@ k_walker_rev(KArgs ka) {
     constexpr int NIT = (NPR + 63) / 64;
     T tc[NIT][8], jc[NIT], ja[NIT];
     int pk[NIT], pi2[NIT];
+    unsigned prow[NIT];
 #pragma unroll
     for (int u = 0; u < NIT; ++u) {
       // pair (k, i) of this slot from the constant table (PairTab)
-      const unsigned code = pair_tab<N>.v[pi][lane + 64 * u];
+      const unsigned code = uat(&pair_tab<N>.v[pi][0], (unsigned)lane)[64 * u];
       const int k = code & 15, i = (code >> 4) & 15;
       pk[u] = k;
       pi2[u] = i;
-      jc[u] = P[Ly::jee_c + k * N + i];
-      ja[u] = P[Ly::jee_a + k * N + i];
+      prow[u] = code >> 8;   // k N + i
+      jc[u] = *uat(P + Ly::jee_c, prow[u]);
+      ja[u] = *uat(P + Ly::jee_a, prow[u]);
     }
 #pragma unroll
     for (int u = 0; u < NIT; ++u) {
-      const int k = pk[u], i = pi2[u];
       // loaded on every lane (pi's pairs of iteration 0 select their own values)
-      const T* tp = Wc + WC::pt + (k * N + i) * 8;
+      const T* tp = uat(Wc + WC::pt, prow[u] * 8);
 #pragma unroll
       for (int o = 0; o < 8; ++o) tc[u][o] = tp[o];
     }
@@ -1947,8 +1986,8 @@ k_walker_rev(KArgs ka) {
   const T sumsq = wave_sum(gd * gd);
   const T lpsi = logdet + (fwd_reg ? jsum_p : wave_sum(jv + jve));
   const auto* kl = late_args();
-  if (kl->grad && dir) ((T*)kl->grad)[(size_t)conf * 3 * N + 3 * le + lc] = g;
-  if (kl->gown && dir && le == pi) ((T*)kl->gown)[(size_t)conf * 3 + lc] = g;
+  if (kl->grad && dir) *uat((T*)kl->grad + (size_t)conf * 3 * N, (unsigned)(3 * le + lc)) = g;
+  if (kl->gown && dir && le == pi) *uat((T*)kl->gown + (size_t)conf * 3, (unsigned)lc) = g;
   if (lane == 0) {
     if (kl->logabs) ((T*)kl->logabs)[conf] = lpsi;
     if (kl->phase) ((T*)kl->phase)[conf] = f_atan2(phi, phr);

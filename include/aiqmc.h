@@ -61,12 +61,12 @@ typedef struct aiqmc_cfg {
   int32_t device;                /* HIP device ordinal                         */
   const double* atoms;           /* [A*3] bohr                                 */
   const double* charges;         /* [A]   (Jastrow e-n + potential charges)    */
-  const int32_t* spin_up_indices;   /* [n_up]   spin_indices.py:38-45          */
-  const int32_t* spin_down_indices; /* [n_down]                                */
+  const int32_t* spin_up_indices;   /* [n_up]   spin_indices.py:38-45; with    */
+  const int32_t* spin_down_indices; /* [n_down] a permutation of 0..N-1        */
   const int32_t* parallel_indices;  /* [2*n_parallel] row-major (2,n_par)      */
   int32_t n_parallel;               /* spin_indices.py:5-19                    */
   const int32_t* antiparallel_indices; /* [2*n_antiparallel]                   */
-  int32_t n_antiparallel;
+  int32_t n_antiparallel;              /* == n_up * n_down                     */
   int32_t hidden_dims[3][2];     /* must be ((4,4),(4,4),(4,4)) (nn.py:525)   */
   int32_t hidden_dims_ynlm[3];   /* must be (6,6,6)             (nn.py:526)   */
 } aiqmc_cfg;

@@ -82,8 +82,20 @@ def alternating_spins(n: int) -> np.ndarray:
     return np.array([1.0 if i % 2 == 0 else -1.0 for i in range(n)])
 
 
+def pattern_spins(pattern: str, n: int) -> np.ndarray:
+    """Spins of an explicit pattern: one 'u' (+1) or 'd' (-1) per electron slot, both occurring."""
+    if len(pattern) != n or set(pattern) != {"u", "d"}:
+        raise ValueError(f"spin pattern {pattern!r}: need {n} letters u/d with both occurring")
+    return np.array([1.0 if ch == "u" else -1.0 for ch in pattern])
+
+
 def make_system(name: str) -> System:
-    """Systems used by BASELINE.json configs (all-electron, alternating spins)."""
+    """Systems used by BASELINE.json configs (all-electron, alternating spins).
+
+    "<system>@<pattern>" sets the spins slot by slot instead ("Z4@uuud", "C_ecp@uuud",
+    "Z4-3@duddudd"): spin-polarised systems, minority-first orderings and n_down > n_up."""
+    full = name
+    name, at, pattern = full.partition("@")
     if name == "H2":
         atoms = np.array([[0.0, 0.0, -0.7], [0.0, 0.0, 0.7]])
         charges = np.array([1.0, 1.0])
@@ -126,11 +138,14 @@ def make_system(name: str) -> System:
         atoms = np.zeros((1, 3)) if len(zs) == 1 else sites[:len(zs)]
         charges = np.array(zs)
     else:
-        raise KeyError(name)
+        raise KeyError(full)
     n = int(charges.sum())
-    spins = alternating_spins(n) if name != "C2_ecp" else np.array([1.0] * (n // 2) + [-1.0] * (n - n // 2))
+    if at:
+        spins = pattern_spins(pattern, n)
+    else:
+        spins = alternating_spins(n) if name != "C2_ecp" else np.array([1.0] * (n // 2) + [-1.0] * (n - n // 2))
     nup = int((spins > 0).sum())
-    return System(name, atoms.astype(np.float64), charges.astype(np.float64), spins, (nup, n - nup))
+    return System(full, atoms.astype(np.float64), charges.astype(np.float64), spins, (nup, n - nup))
 
 
 # ----------------------------------------------------------------------------

@@ -92,6 +92,40 @@ def test_create_rejects_bad_config_without_touching_gpu():
     assert lib.aiqmc_create(None, ctypes.byref(h)) != 0
 
 
+def test_create_rejects_inconsistent_spin_tables_without_touching_gpu():
+    """Spin tables that are no permutation of 0..N-1 and pair tables that contradict nspins are
+    AIQMC_EINVAL before any device call (the GPU twin: test_inconsistent_spin_tables_are_refused)."""
+    from aiqmc import _lib
+    from oracle import system
+    lib = _lib.load()
+    i32 = lambda a: np.ascontiguousarray(np.asarray(a, dtype=np.int32).reshape(-1))
+
+    def create(nspins, up, dn, pattern):
+        par, anti, npar, nanti = system.jastrow_indices_ee(system.pattern_spins(pattern, 4), 4)
+        keep = [i32(up), i32(dn), i32(par), i32(anti), np.zeros(3), np.array([4.0])]
+        p = lambda a, t: a.ctypes.data_as(ctypes.POINTER(t))
+        cfg = _lib.AiqmcCfg()
+        cfg.nelectrons, cfg.natoms, cfg.dtype, cfg.device = 4, 1, 1, 0
+        cfg.nspins[0], cfg.nspins[1] = nspins
+        cfg.spin_up_indices, cfg.spin_down_indices = p(keep[0], ctypes.c_int32), p(keep[1], ctypes.c_int32)
+        cfg.parallel_indices, cfg.antiparallel_indices = p(keep[2], ctypes.c_int32), p(keep[3], ctypes.c_int32)
+        cfg.n_parallel, cfg.n_antiparallel = npar, nanti
+        cfg.atoms, cfg.charges = p(keep[4], ctypes.c_double), p(keep[5], ctypes.c_double)
+        for l in range(3):
+            cfg.hidden_dims[l][0], cfg.hidden_dims[l][1], cfg.hidden_dims_ynlm[l] = 4, 4, 6
+        h = ctypes.c_void_p()
+        return lib.aiqmc_create(ctypes.byref(cfg), ctypes.byref(h)), _lib.last_error(), h
+
+    for nspins, up, dn, pattern, what in [
+            ((2, 2), [0, 0], [1, 3], "udud", "permutation of 0..N-1: electron 2 is in neither"),
+            ((2, 2), [0, 2], [2, 3], "udud", "electron 2 is in spin_up_indices and in spin_down_indices"),
+            ((1, 3), [1], [0, 3, 3], "dudd", "electron 2 is in neither"),
+            ((2, 2), [0, 2], [1, 3], "uuud", "n_antiparallel = 3 contradicts the spin tables: nspins[0] * nspins[1] = 4"),
+            ((3, 1), [0, 1, 2], [3], "udud", "n_antiparallel = 4 contradicts")]:
+        rc, msg, h = create(nspins, up, dn, pattern)
+        assert rc == -1 and what in msg and not h.value, (rc, msg)
+
+
 def test_null_context_calls_fail_cleanly():
     from aiqmc import _lib
     lib = _lib.load()

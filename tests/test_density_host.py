@@ -25,17 +25,20 @@ ONE = 1 << 32
 TOL = {torch.float32: 1e-4, torch.float64: 1e-10}
 FIELDS = ("total", "skipped", "grid", "grid_out", "radial", "radial_out", "pair", "pair_out")
 
-# name -> (atoms [A, 3], electrons per atom); alternating spins, slot 0 up
+# name -> (atoms [A, 3], electrons per atom); alternating spins, slot 0 up, unless the name carries
+# its spins after "@", one u / d per slot (oracle/system.py)
 SYSTEMS = {
     "H2": ([[0.0, 0.0, -0.7], [0.0, 0.0, 0.7]], [1, 1]),
     "Be": ([[0.0, 0.0, 0.0]], [4]),
     "Z5": ([[0.0, 0.0, 0.0]], [5]),                      # odd N, nspins (3, 2)
     "N2": ([[0.0, 0.0, -1.0372], [0.0, 0.0, 1.0372]], [7, 7]),
+    "Z5@duddd": ([[0.0, 0.0, 0.0]], [5]),                # spin-polarised, minority first: nspins (1, 4)
 }
 GRID = ((-2.5, -3.0, -3.5), (2.5, 3.0, 3.5), (6, 9, 16))
 RADIAL = (4.0, 16)
 PAIR = (5.0, 12)
-SEEDS = {"H2": 2, "Be": 3, "Z5": 3, "N2": 14}   # the first seeds without an edge sample at tol 1e-4
+# the first seeds without an edge sample at tol 1e-4 (the walkers do not depend on the spins)
+SEEDS = {"H2": 2, "Be": 3, "Z5": 3, "N2": 14, "Z5@duddd": 3}
 BMAX = 70
 
 
@@ -43,7 +46,9 @@ def geometry(name):
     atoms, per = SYSTEMS[name]
     atoms = np.asarray(atoms, dtype=np.float64)
     n = int(sum(per))
-    spins = np.array([1.0 if i % 2 == 0 else -1.0 for i in range(n)])
+    pattern = name.partition("@")[2]
+    assert len(pattern) in (0, n)
+    spins = np.array([1.0 if (ch == "u" if pattern else i % 2 == 0) else -1.0 for i, ch in enumerate(pattern or "u" * n)])
     return atoms, per, spins
 
 

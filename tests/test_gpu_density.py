@@ -4,7 +4,8 @@ tests/test_density_host.py (`replica`: the bin rule written out directly, nothin
 Every comparison first asserts that its seeded input has no edge sample (|f - rint(f)| <= 1e-4 for a
 float32 context, f <= 64 in these tests; 1e-10 for float64) and then demands exact integer equality
 of every accumulator word.  Systems: H2 (N = 2: the up-up and down-down pair channels stay empty),
-Be (4, 1), Z5 (N = 5, nspins (3, 2): odd, unequal channels), N2 (14, 2).  Batches 1 and 70 (70 is
+Be (4, 1), Z5 (N = 5, nspins (3, 2): odd, unequal channels), N2 (14, 2), Z5@duddd (spin-polarised,
+nspins (1, 4), the one up electron in slot 1).  Batches 1 and 70 (70 is
 neither a wave nor a workgroup multiple, and more than one workgroup of 32 walkers); 6-16 bins per
 axis.  The replica of a (system, families, weights) case is computed once and shared.
 """
@@ -113,6 +114,30 @@ def test_weighted_words_and_conservation(dtype, name):
                                   [tot * (nup * (nup - 1) // 2), tot * (ndn * (ndn - 1) // 2), tot * nup * ndn])
     if name == "H2":
         assert c["pair"].reshape(3, -1)[:2].sum() == 0 and c["pair_out"][:2].sum() == 0
+
+
+@DTYPES
+def test_polarised_minority_first_channel_totals(dtype):
+    """Z5@duddd, nspins (1, 4) with the one up electron in slot 1: every word equals the replica, the
+    spin-resolved grid totals are n_up B and n_down B (not swapped), the pair channels hold
+    n_up (n_up - 1) / 2 = 0, n_down (n_down - 1) / 2 = 6 and n_up n_down = 4 pairs per walker, and the
+    up channel is exactly what slot 1 alone gives."""
+    name, B = "Z5@duddd", H.BMAX
+    ctx = _ctx(name, dtype)
+    assert ctx.nspins == (1, 4)
+    acc, lay = _run(ctx, walkers(name), ALL)
+    _assert_equal(acc, lay, _ref(name, B, ("grid", "radial", "pair"), dtype))
+    c = _named(acc, lay)
+    assert c["total"][0] == B * H.ONE
+    np.testing.assert_array_equal(c["grid"].reshape(2, -1).sum(1) + c["grid_out"], [1 * B * H.ONE, 4 * B * H.ONE])
+    np.testing.assert_array_equal(c["radial"].reshape(2, -1).sum(1) + c["radial_out"], [1 * B * H.ONE, 4 * B * H.ONE])
+    np.testing.assert_array_equal(c["pair"].reshape(3, -1).sum(1) + c["pair_out"], [0, 6 * B * H.ONE, 4 * B * H.ONE])
+    atoms, _, _ = H.geometry(name)
+    slot1, edges = replica(walkers(name).reshape(B, 5, 3)[:, 1].reshape(B, 3), atoms, np.array([1.0]), tol=TOL[dtype],
+                           grid=GRID, radial=RADIAL)
+    assert edges == 0
+    np.testing.assert_array_equal(c["grid"].reshape(2, -1)[0], slot1["grid"][0].reshape(-1))
+    np.testing.assert_array_equal(c["radial"].reshape(2, -1)[0], slot1["radial"][0].reshape(-1))
 
 
 @pytest.mark.parametrize("name", ["Z5", "N2"])

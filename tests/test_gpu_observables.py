@@ -6,7 +6,8 @@ Shapes: the smallest that take each dispatch of the value launch -- H2 (2,2) fou
 per wave and a single pair, Be (4,1) four per wave, (5,1) with nspins (3,2) two per wave, unequal
 channels and odd N, (8,2) the two-per-wave boundary, (9,1) with nspins (5,4) the first one-wave
 shape, N2 (14,2).  Batches 5 (no multiple of a packing factor: the partial last wave) and 8.
-Alternating spins and randomised auxiliary parameters, as tests/test_gpu_shapes.py.  The walkers are
+Spin-polarised: Z4@dudd (1,3), Z5@uuuud (4,1), Z9@uuuuduuuu (8,1), as tests/test_gpu_spin_polarised.py.
+Otherwise alternating spins; randomised auxiliary parameters, as tests/test_gpu_shapes.py.  The walkers are
 rounded to float32 so that both dtypes and the oracle see the same positions.
 
 Tolerances (none of them new):
@@ -29,7 +30,10 @@ import torch
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CASES = ["H2", "Be", "Z5", "Z4-4", "Z9", "N2"]
+# spin-polarised walkers, "<system>@<u/d per slot>" (oracle/system.py): (1,3) with n_down > n_up, (4,1)
+# two per wave, (8,1) one wave -- the pair index k runs over n_up * n_down with k / n_down, k % n_down
+POLARISED = ["Z4@dudd", "Z5@uuuud", "Z9@uuuuduuuu"]
+CASES = ["H2", "Be", "Z5", "Z4-4", "Z9", "N2"] + POLARISED
 BMAX = 8
 # (rtol, atol) of dlogabs and atol of cos / sin of dphase: the single-value bounds, doubled
 TOL = {torch.float64: (2e-10, 2e-10, 2e-9), torch.float32: (2e-5, 4e-4, 4e-4)}
@@ -133,6 +137,29 @@ def test_pairs_are_logpsi_differences_bitwise(dtype, name):
     print(f"{name} {dtype}: max |dlogabs - logpsi difference| {(dl.reshape(B, K) - dl_h).abs().max().item():.3g}")
     assert torch.equal(dl.reshape(B, K), dl_h)
     assert torch.equal(dp.reshape(B, K), dp_h)
+
+
+@pytest.mark.parametrize("name", POLARISED)
+def test_diagonal_and_pair_shapes_follow_nspins(name):
+    """aiqmc.observables._s2_diagonal is S_z (S_z + 1) + the minority count whichever channel is the
+    minority, the pair outputs are [B, n_up, n_down] in that order, and the kernel's S2_L is that
+    diagonal minus the sum of its own pair ratios: K + 1 additions and, per term, exp, cos / sin and
+    two products, each within a few units of roundoff of the magnitudes summed."""
+    from aiqmc import observables
+    s, params, pos, _, _, _, _ = _case(name)
+    nup, ndn = s.nspins
+    assert nup != (s.nelectrons + 1) // 2
+    sz = 0.5 * abs(nup - ndn)
+    diag = observables._s2_diagonal((nup, ndn))
+    assert diag == observables._s2_diagonal((ndn, nup)) == sz * (sz + 1.0) + min(nup, ndn)
+    ctx = _ctx(s, params, torch.float64)
+    s2, dl, dp = ctx.spin_squared(torch.tensor(pos, device="cuda"), want_pairs=True)
+    torch.cuda.synchronize()
+    assert dl.shape == (BMAX, nup, ndn) and dp.shape == (BMAX, nup, ndn)
+    ratio = (torch.exp(dl) * torch.complex(torch.cos(dp), torch.sin(dp))).cpu().numpy()
+    K = nup * ndn
+    bound = (K + 9) * 2.0 ** -53 * (diag + np.abs(ratio).sum((1, 2)))
+    assert np.all(np.abs(s2.cpu().numpy() - (diag - ratio.sum((1, 2)))) <= bound)
 
 
 @pytest.mark.parametrize("name,B,chunk", [("H2", 8, 5), ("Z5", 7, 16), ("N2", 5, 100)])

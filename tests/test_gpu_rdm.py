@@ -2,7 +2,7 @@
 (oracle/network.py) on numpy-built moved configurations, as tests/test_gpu_observables.py does for S^2.
 
 Systems: H2 (2,2) four configurations per wave, Z5 with nspins (3,2) two per wave and odd N, N2
-(14,2).  Batches 5 (partial last wave, one partial group) and 8; H2 also 37 (two groups, the second
+(14,2); spin-polarised Z5@uuuud (4,1) and Z5@duddd (1,4), the minority first.  Batches 5 (partial last wave, one partial group) and 8; H2 also 37 (two groups, the second
 partial).  S = 3 points per walker for H2 and Z5 (S n_sigma is no multiple of 4), 1 for N2.  Bases:
 "p3" one p shell (norb = 3, below one MFMA tile) and "spd17" s, p and d shells on two centres
 (nao = 20) with a random [2][20][17] coefficient matrix (two tiles with a tail, rho_up != rho_down).
@@ -38,8 +38,10 @@ pytestmark = pytest.mark.gpu
 
 F32, F64 = torch.float32, torch.float64
 DTYPES = pytest.mark.parametrize("dtype", [F64, F32], ids=["fp64", "fp32"])
-SAMPLES = {"H2": 3, "Z5": 3, "N2": 1}
-BMAX = {"H2": 37, "Z5": 8, "N2": 8}
+# spin-polarised, "<system>@<u/d per slot>" (oracle/system.py): (4,1), and (1,4) with the minority first
+POLARISED = ["Z5@uuuud", "Z5@duddd"]
+SAMPLES = {"H2": 3, "Z5": 3, "N2": 1, "Z5@uuuud": 3, "Z5@duddd": 3}
+BMAX = {"H2": 37, "Z5": 8, "N2": 8, "Z5@uuuud": 8, "Z5@duddd": 8}
 QC, QS, QP = np.array([[0.0, 0.0, -0.7], [0.1, 0.0, 0.8]]), np.array([1.25, 1.5]), np.array([0.625, 0.375])
 NORMAL_BOUND = 1.31e-5      # tests/test_gpu_philox.py: device Box-Muller against the float64 replica
 
@@ -163,7 +165,8 @@ def _dev(a, dtype):
     return torch.tensor(a, device="cuda", dtype=dtype)
 
 
-CASES = [("H2", 5), ("H2", 8), ("H2", 37), ("Z5", 5), ("Z5", 8), ("N2", 5), ("N2", 8)]
+CASES = [("H2", 5), ("H2", 8), ("H2", 37), ("Z5", 5), ("Z5", 8), ("N2", 5), ("N2", 8)] + [(n, B) for n in POLARISED
+                                                                                          for B in (5, 8)]
 
 
 @pytest.mark.parametrize("kind", ["p3", "spd17"])
@@ -189,6 +192,20 @@ def test_matrix_matches_oracle(dtype, name, B, kind):
     m = got[1:].reshape(2, K, K, 2)
     if kind == "spd17":
         assert np.abs(m[0] - m[1]).max() > 1e-3 * np.abs(m).max()
+    if name in POLARISED:
+        # the trace of a channel's block is a sum over that channel's n_up or n_down electron slots.  In
+        # this finite, non-orthogonal basis it is not the electron count itself, so it is held to the
+        # replica's trace within the summed diagonal bounds; and the replica alone shows that the
+        # channels cannot be swapped unnoticed: with the slot lists exchanged its traces move by
+        # more than twice those bounds.
+        from oracle import system
+        swapped = system.make_system(name.translate(str.maketrans("ud", "du")))
+        assert swapped.nspins == s.nspins[::-1] and s.nspins[0] != s.nspins[1]
+        ref_sw, bound_sw = reference(swapped, basis, pos[:B], rp[:B], wb, dl[:B], dp[:B], dtype)
+        tr = lambda v: np.einsum("siic->sc", v[1:].reshape(2, K, K, 2))
+        tb = np.maximum(tr(bound), tr(bound_sw)[::-1])
+        assert np.all(np.abs(tr(got) - tr(ref)) <= tr(bound))
+        assert np.all(np.abs(tr(ref)[:, 0] - tr(ref_sw)[:, 0]) > 2 * tb[:, 0]), (tr(ref), tr(ref_sw), tb)
 
 
 @pytest.mark.parametrize("name", ["H2", "Z5", "N2"])

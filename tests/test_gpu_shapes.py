@@ -13,7 +13,9 @@ randomised auxiliary parameters:
   fp32: log|psi| and E_L against the same fp64 oracle (the reference's dtype, the parity
         suite's fp32 tolerances).
 Outside the built set aiqmc_create refuses with AIQMC_EUNSUPPORTED and a message naming the
-limit (N = 17; A = 6)."""
+limit (N = 17; A = 6), an empty spin channel likewise; spin tables that are no permutation of the
+electron slots and pair tables that contradict nspins are AIQMC_EINVAL.  Spin-polarised systems:
+tests/test_gpu_spin_polarised.py."""
 import numpy as np
 import pytest
 import torch
@@ -124,6 +126,32 @@ def test_shape_outside_the_built_set_is_refused(n, a, what):
     with pytest.raises(Exception) as ei:
         _lib.Context(n, a, (len(up), len(dn)), atoms, charges, up, dn, par, anti, dtype=torch.float64, device=0)
     assert what in str(ei.value)
+
+
+@pytest.mark.parametrize("nspins,up,dn,pair_spins,code,what", [
+    ((2, 2), [0, 0], [1, 3], "udud", -1, "permutation of 0..N-1: electron 2 is in neither"),          # a slot twice
+    ((2, 2), [0, 2], [2, 3], "udud", -1, "electron 2 is in spin_up_indices and in spin_down_indices"),
+    ((1, 3), [1], [0, 3, 3], "dudd", -1, "electron 2 is in neither"),
+    ((2, 2), [0, 2], [1, 3], "uuud", -1, "n_antiparallel = 3 contradicts the spin tables: nspins[0] * nspins[1] = 4"),
+    ((3, 1), [0, 1, 2], [3], "udud", -1, "n_antiparallel = 4 contradicts"),
+    ((4, 0), [0, 1, 2, 3], [], "uuuu", -2, "both spin channels must be occupied"),
+    ((0, 4), [], [0, 1, 2, 3], "dddd", -2, "both spin channels must be occupied"),
+], ids=["repeated_up", "up_and_down", "repeated_down", "anti_too_few", "anti_too_many", "no_down", "no_up"])
+def test_inconsistent_spin_tables_are_refused(nspins, up, dn, pair_spins, code, what):
+    """aiqmc_create on four electrons: spin tables that are no permutation of 0..N-1 (a repeated
+    slot is a repeated determinant row) and pair tables that contradict nspins are AIQMC_EINVAL (-1)
+    with a message naming the offender; an empty spin channel is AIQMC_EUNSUPPORTED (-2)."""
+    from aiqmc import _lib
+    from oracle import system
+    spins = np.array([1.0 if ch == "u" else -1.0 for ch in pair_spins])
+    par, anti, _, _ = system.jastrow_indices_ee(spins, 4)
+    with pytest.raises(RuntimeError) as ei:
+        _lib.Context(4, 1, nspins, np.zeros((1, 3)), np.array([4.0]), np.array(up, dtype=np.int32),
+                     np.array(dn, dtype=np.int32), par, anti, dtype=torch.float64, device=0)
+    assert what in str(ei.value) and f"({code})" in str(ei.value), str(ei.value)
+    # and the consistent tables of the same spins are accepted
+    s = system.make_system("Z4@" + ("uuud" if pair_spins in ("uuuu", "dddd") else pair_spins))
+    assert _lib.Context.for_system(s, torch.float64).nparams > 0
 
 
 @pytest.mark.parametrize("shape", [(7, 1), (5, 3), (13, 3), (16, 3), (10, 5)], ids=lambda sh: f"N{sh[0]}A{sh[1]}")

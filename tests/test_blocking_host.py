@@ -16,37 +16,16 @@ tests/test_gpu_blocking.py):
 """
 import ctypes
 import os
-import socket
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
+import support
 from conftest import ROOT
+from replicas_estimators import _sums, assert_words, order_bound, pair_reblock
 
-U = 2.0 ** -53
 TOL_DIRECT = 1e-12
-
-
-def _sums(blocks, B, K):
-    """Per-level sums of a list of block arrays [nb, K, B]: n [L], S [L, K], Q [L, K (K + 1) / 2]
-    and the sums of the absolute terms aS, aQ (numpy's summation order)."""
-    iu = np.triu_indices(K)
-    L = len(blocks)
-    out = {"n": np.zeros(L), "S": np.zeros((L, K)), "Q": np.zeros((L, iu[0].size)), "aS": np.zeros((L, K)),
-           "aQ": np.zeros((L, iu[0].size))}
-    for k, v in enumerate(blocks):
-        if v.shape[0] == 0:
-            continue
-        out["n"][k] = v.shape[0] * B
-        out["S"][k] = v.sum(axis=(0, 2))
-        out["aS"][k] = np.abs(v).sum(axis=(0, 2))
-        p = v[:, iu[0]] * v[:, iu[1]]
-        out["Q"][k] = p.sum(axis=(0, 2))
-        out["aQ"][k] = np.abs(p).sum(axis=(0, 2))
-    return out
 
 
 def direct_reblock(trace, shift, L):
@@ -58,42 +37,6 @@ def direct_reblock(trace, shift, L):
         nb = T >> k
         blocks.append(v[:nb << k].reshape(nb, 1 << k, K, B).mean(axis=1) if nb else np.zeros((0, K, B)))
     return _sums(blocks, B, K), blocks
-
-
-def pair_reblock(trace, shift, L):
-    """The same blocks as (first + second) / 2 of the level below: the recurrence's own terms."""
-    T, K, B = trace.shape
-    v = trace.astype(np.float64) - np.asarray(shift, dtype=np.float64)[None, :, None]
-    blocks = []
-    for k in range(L):
-        blocks.append(v)
-        nb = v.shape[0] // 2
-        v = (v[0:2 * nb:2] + v[1:2 * nb:2]) / 2.0
-    return _sums(blocks, B, K), blocks
-
-
-def words_of(acc):
-    """(t, n [L], S [L, K], Q [L, Kq]) of an accumulator, numpy float64 on the host."""
-    a = acc.acc.detach().cpu().numpy()
-    w = a[1 + acc.K:].reshape(acc.L, acc.M)
-    return a[0], w[:, 0].copy(), w[:, 1:1 + acc.K].copy(), w[:, 1 + acc.K:].copy()
-
-
-def assert_words(acc, ref, T, factor, what=""):
-    """Counts and t exact; every S and Q word within factor * sum |term| of the reference, where
-    factor is a float or a callable of the word's term count."""
-    t, n, S, Q = words_of(acc)
-    assert t == T, (what, t)
-    np.testing.assert_array_equal(n, ref["n"], err_msg=what)
-    f = np.array([factor(x) if callable(factor) else factor for x in ref["n"]])[:, None]
-    for got, want, scale, name in ((S, ref["S"], ref["aS"], "S"), (Q, ref["Q"], ref["aQ"], "Q")):
-        err, bound = np.abs(got - want), f * scale
-        assert np.all(err <= bound), (what, name, float((err - bound).max()), float(err.max()))
-
-
-def order_bound(n):
-    """2 n u: two summation orders of the same n fp64 terms, as a factor of sum |term|."""
-    return 2.0 * n * U
 
 
 def feed(trace, L, shift=None, dtype=torch.float64, device="cpu"):
@@ -297,16 +240,7 @@ def _two_rank_case(rank, world, extra=False):
 
 def _run_ranks(tmp_path, mode):
     world = 2
-    with socket.socket() as sk:
-        sk.bind(("127.0.0.1", 0))
-        port = sk.getsockname()[1]
-    procs = []
-    for r in range(world):
-        env = dict(os.environ, RANK=str(r), WORLD_SIZE=str(world), LOCAL_RANK=str(r), MASTER_ADDR="127.0.0.1",
-                   MASTER_PORT=str(port))
-        procs.append(subprocess.Popen([sys.executable, "-c", _WORKER, ROOT, str(tmp_path), mode], env=env))
-    for p in procs:
-        assert p.wait(timeout=240) == 0
+    assert support.run_ranks(_WORKER, world, [ROOT, str(tmp_path), mode], timeout=240) == [0] * world
 
 
 def test_two_rank_gloo_reduction_equals_one_process(tmp_path):

@@ -8,13 +8,14 @@ least 0.1 bohr from every nucleus; two gloo ranks against one process to 1e-12 r
 """
 import ctypes
 import os
-import socket
 
 import numpy as np
 import pytest
 import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
+
+import support
 
 SITES = np.array([[0.0, 0.0, -1.0], [0.0, 0.0, 1.0], [1.2, 0.7, 0.3], [-0.9, 1.1, -0.4], [0.3, -1.3, 0.8]])
 
@@ -287,14 +288,6 @@ def test_driver_needs_a_checkpoint(tmp_path):
 
 
 # ----------------------------------------------------------------------------- two ranks
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
 def _worker(rank, world, port, q):
     import sys
     from conftest import PKG
@@ -317,7 +310,7 @@ def test_two_ranks_equal_one_process():
     in one process."""
     from aiqmc.correlatedsamples import estimator
     world = 2
-    port = _free_port()
+    port = support.free_port()
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     procs = [ctx.Process(target=_worker, args=(r, world, port, q)) for r in range(world)]

@@ -7,7 +7,6 @@ single-process statistics of the concatenated walker set, and that
 psum/pmean/all_gather follow the reference's constants.py semantics.
 """
 import os
-import socket
 
 import numpy as np
 import pytest
@@ -15,13 +14,7 @@ import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
+import support
 
 
 def _worker(rank, world, port, q):
@@ -48,7 +41,7 @@ def _worker(rank, world, port, q):
 def test_pmean_stats_matches_global(world):
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    port = _free_port()
+    port = support.free_port()
     procs = [ctx.Process(target=_worker, args=(r, world, port, q)) for r in range(world)]
     for p in procs:
         p.start()
@@ -101,7 +94,7 @@ def test_clipping_and_gradient_pmean_match_global(world):
     """loss.py:73-135 statistics over ranks (pmean'd mean, TV and clipped mean) equal the
     single-device computation on the concatenated batch; the gradient pmean is the rank mean."""
     from oracle import loss as oloss
-    port = _free_port()
+    port = support.free_port()
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     procs = [ctx.Process(target=_clip_worker, args=(r, world, port, q)) for r in range(world)]
@@ -161,7 +154,7 @@ def test_dmc_checkpoint_cadence_is_collective(tmp_path):
     world = 2
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    port = _free_port()
+    port = support.free_port()
     procs = [ctx.Process(target=_ckpt_worker, args=(r, world, port, str(tmp_path), q)) for r in range(world)]
     for p in procs:
         p.start()

@@ -12,7 +12,6 @@ formulas on the concatenated batch (oracle.loss.energy_gradient_complex, a liter
 of loss.py:220-270) to 1e-12, with exactly 3 all-reduces per step (2 without clipping).
 """
 import os
-import socket
 
 import numpy as np
 import pytest
@@ -20,15 +19,9 @@ import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
+import support
+
 B_RANK, P = 48, 37
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
 
 
 def _global_batch(world, complex_e):
@@ -86,7 +79,7 @@ def _worker(rank, world, port, q):
 @pytest.mark.parametrize("world", [2, 4])
 def test_fused_levels_match_concatenated_batch(world):
     from oracle import loss as oloss
-    port = _free_port()
+    port = support.free_port()
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     procs = [ctx.Process(target=_worker, args=(r, world, port, q)) for r in range(world)]

@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 import torch
 
-import test_gpu_reductions as _red     # the comb inputs of the GPU comparisons
+import replicas_loss as _red     # the comb inputs of the GPU comparisons
 from oracle import dmc as odmc
 
 

@@ -26,9 +26,13 @@ from a few seconds, with the oracle out of reach).  The guarantee is static inst
 is 64-bit scalar arithmetic in every kernel, only the offset within one record is 32-bit, and
 k_walker_rev static_asserts every record and table size it indexes (URecordFits).
 """
+import functools
+
 import numpy as np
 import pytest
 import torch
+
+import support
 
 pytestmark = pytest.mark.gpu
 
@@ -39,22 +43,16 @@ TSTEP = 0.05
 _ids = lambda sh: f"N{sh[0]}A{sh[1]}"
 
 
-def _name(n, a):
-    zs = [n // a + (1 if k < n % a else 0) for k in range(a)]
-    return "Z" + "-".join(str(z) for z in zs)
+_REF = {}
 
 
-_SYS, _REF = {}, {}
-
-
+@functools.lru_cache(maxsize=None)
 def _system(shape):
-    if shape not in _SYS:
-        from oracle import network, system
-        n, a = shape
-        s = system.make_system(_name(n, a))
-        params = system.init_params(np.random.default_rng(900 + 3 * n + a), s, randomize_aux=True)
-        _SYS[shape] = (s, params, network.Network(s), network.to_torch(params))
-    return _SYS[shape]
+    """(system, params, oracle network, oracle params), cached per shape."""
+    from oracle import network
+    n, a = shape
+    s, params, _ = support.seeded_case(support.z_name(n, a), 900 + 3 * n + a, randomize_aux=True)
+    return s, params, network.Network(s), network.to_torch(params)
 
 
 def _reference(shape, B):
@@ -98,14 +96,11 @@ def _oracle_values(shape, x):
 @pytest.mark.parametrize("B", BATCHES, ids=lambda b: f"B{b}")
 @pytest.mark.parametrize("shape", SHAPES, ids=_ids)
 def test_sweep_and_values_match_oracle(shape, B, dtype):
-    from oracle import system
-    from aiqmc import _lib
     s, params, _, _ = _system(shape)
     pos, (g1, g2, u), x_ref, cond = _reference(shape, B)
     N = shape[0]
     idx = torch.arange(N)
-    ctx = _lib.Context.for_system(s, dtype)
-    ctx.set_params(system.flatten_params(params))
+    ctx = support.make_ctx(s, dtype, params)
     x = torch.tensor(pos, dtype=dtype, device="cuda").contiguous()
     acc = ctx.mc_step(x, 1, TSTEP, count_accepts=True, gauss1=g1[None],
                       gauss2=g2.reshape(1, B, N, N, 3)[:, :, idx, idx, :].contiguous(), u=u[None])

@@ -24,34 +24,13 @@ import numpy as np
 import pytest
 import torch
 
+import support
+
 pytestmark = pytest.mark.gpu
 
 # shape -> (walkers, seed of the draws); seeds found by scanning 0, 1, ... on the oracle for MARGIN
 CASES = {(9, 1): (3, 0), (14, 2): (3, 0), (16, 1): (2, 1)}
 MARGIN = 1e-2
-
-
-def _name(n, a):
-    """charges: N split over the A atoms, the remainder on the first ones (as test_gpu_shapes.py)."""
-    zs = [n // a + (1 if k < n % a else 0) for k in range(a)]
-    return "Z" + "-".join(str(z) for z in zs)
-
-
-def _draws(seed, B, N):
-    rng = np.random.default_rng(seed)
-    g1 = torch.tensor(rng.standard_normal((1, B, 3 * N)))
-    g2 = torch.tensor(rng.standard_normal((1, B, N, 3 * N)))
-    u = torch.tensor(rng.uniform(size=(1, B, N)))
-    return g1, g2, u
-
-
-def _oracle_sweep(s, params, pos, draws):
-    """(new positions, acceptance ratios [B, N]) of one fp64 oracle sweep."""
-    from oracle import mcstep, network
-    g1, g2, u = draws
-    x, acc = mcstep.walkers_update(network.Network(s), network.to_torch(params), torch.tensor(pos), g1[0], g2[0],
-                                   u[0], 0.05)
-    return x.numpy(), acc.numpy()
 
 
 _REF = {}
@@ -60,15 +39,11 @@ _REF = {}
 def _case(shape):
     """(system, params, walkers, draws, oracle positions, oracle accept mask), cached per shape."""
     if shape not in _REF:
-        from oracle import system
         n, a = shape
         B, seed = CASES[shape]
-        s = system.make_system(_name(n, a))
-        rng = np.random.default_rng(300 + 3 * n + a)
-        params = system.init_params(rng, s, randomize_aux=True)
-        pos = system.init_electrons(rng, s.atoms, s.charges, B, 1.0)
-        draws = _draws(seed, B, n)
-        x_ref, acc = _oracle_sweep(s, params, pos, draws)
+        s, params, pos = support.seeded_case(support.z_name(n, a), 300 + 3 * n + a, B, randomize_aux=True)
+        draws = support.host_draws(seed, B, n)
+        x_ref, acc = support.oracle_sweep(s, params, pos, draws, 0.05)
         u = draws[2][0].numpy()
         gap = np.abs(acc - u)
         print(f"{shape}: min |acceptance - u| = {gap.min():.3e}, accepted {(acc > u).sum()} of {acc.size}")
@@ -77,20 +52,12 @@ def _case(shape):
     return _REF[shape]
 
 
-def _ctx(s, params, dtype):
-    from oracle import system
-    from aiqmc import _lib
-    ctx = _lib.Context.for_system(s, dtype)
-    ctx.set_params(system.flatten_params(params))
-    return ctx
-
-
 def _gpu_sweep(s, params, pos, draws, dtype, reuse):
     """One mc_step sweep on a fresh context; (positions, accepted moves per walker)."""
     N, B = s.nelectrons, pos.shape[0]
     g1, g2, u = draws
     idx = torch.arange(N)
-    ctx = _ctx(s, params, dtype)
+    ctx = support.make_ctx(s, dtype, params)
     ctx.set_proposal_reuse(reuse)
     x = torch.tensor(pos, dtype=dtype, device="cuda").contiguous()
     acc = ctx.mc_step(x, 1, 0.05, count_accepts=True, gauss1=g1,
@@ -124,13 +91,9 @@ def test_handover_sweep_matches_recompute(shape, dtype):
 
 def test_packed_walker_record_sweep_matches_oracle():
     """Be, five walkers (N <= 4: four walkers per wave, the second wave partial)."""
-    from oracle import system
-    s = system.make_system("Be")
-    rng = np.random.default_rng(41)
-    params = system.init_params(rng, s, randomize_aux=True)
-    pos = system.init_electrons(rng, s.atoms, s.charges, 5, 1.0)
-    draws = _draws(11, 5, s.nelectrons)
-    x_ref, _ = _oracle_sweep(s, params, pos, draws)
+    s, params, pos = support.seeded_case("Be", 41, 5, randomize_aux=True)
+    draws = support.host_draws(11, 5, s.nelectrons)
+    x_ref, _ = support.oracle_sweep(s, params, pos, draws, 0.05)
     x, acc = _gpu_sweep(s, params, pos, draws, torch.float64, True)
     assert int(acc.sum()) > 0
     np.testing.assert_allclose(x.cpu().numpy(), x_ref, rtol=1e-9, atol=1e-9)

@@ -17,7 +17,7 @@ import numpy as np
 import pytest
 import torch
 
-from test_blocking_host import assert_words, order_bound, pair_reblock, words_of
+from replicas_estimators import assert_words, order_bound, pair_reblock, words_of
 
 pytestmark = pytest.mark.gpu
 

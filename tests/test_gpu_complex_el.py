@@ -7,19 +7,15 @@ import numpy as np
 import pytest
 import torch
 
+import support
+
 pytestmark = pytest.mark.gpu
 
 
 def _ctx_and_oracle(name, dtype, B, seed):
-    from oracle import network, system
-    from aiqmc import _lib
-    s = system.make_system(name)
-    rng = np.random.default_rng(seed)
-    params = system.init_params(rng, s, randomize_aux=True)
-    pos = system.init_electrons(rng, s.atoms, s.charges, B, 1.0)
-    ctx = _lib.Context.for_system(s, dtype)
-    ctx.set_params(system.flatten_params(params))
-    return s, ctx, network.Network(s), params, pos
+    from oracle import network
+    s, params, pos = support.seeded_case(name, seed, B, randomize_aux=True)
+    return s, support.make_ctx(s, dtype, params), network.Network(s), params, pos
 
 
 @pytest.mark.parametrize("name", ["H2", "Be", "C", "Ne", "N2"])

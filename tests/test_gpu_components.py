@@ -34,6 +34,7 @@ import numpy as np
 import pytest
 import torch
 
+import support
 from conftest import GOLDEN
 
 pytestmark = pytest.mark.gpu
@@ -94,16 +95,8 @@ def _case(name):
 
 
 def _ctx(c, dtype, set_params=True):
-    from aiqmc import _lib
-    s, e = c["s"], c["ecp"]
-    if (s.nelectrons, s.natoms) not in _lib.supported_shapes():
-        pytest.skip(f"({s.nelectrons}, {s.natoms}) not in this library's shape list")
-    ctx = _lib.Context.for_system(s, dtype)
-    if e is not None:
-        ctx.set_ecp_tables(e)
-    if set_params:
-        ctx.set_params(c["params"])
-    return ctx
+    support.skip_unbuilt(c["s"])
+    return support.make_ctx(c["s"], dtype, c["params"] if set_params else None, ecp=c["ecp"])
 
 
 def _run(c, ctx, dtype, sl=slice(None), complex_output=False):

@@ -33,6 +33,8 @@ import numpy as np
 import pytest
 import torch
 
+import support
+
 pytestmark = pytest.mark.gpu
 
 SHAPES = {"H2": (2, 2), "Be": (4, 1), "Z1-1-1": (3, 3), "Z2-2-2-2-2": (10, 5), "CO2_ecp": (16, 3), "N2": (14, 2)}
@@ -64,14 +66,8 @@ def _warp_case(name):
 
 
 def _ctx(s, dtype, params=None, atoms=None):
-    from oracle import system
-    from aiqmc import _lib
-    if (s.nelectrons, s.natoms) not in _lib.supported_shapes():
-        pytest.skip(f"({s.nelectrons}, {s.natoms}) not in this library's shape list")
-    ctx = _lib.Context.for_system(s, dtype, atoms=atoms)
-    if params is not None:
-        ctx.set_params(system.flatten_params(params))
-    return ctx
+    support.skip_unbuilt(s)
+    return support.make_ctx(s, dtype, params, atoms=atoms)
 
 
 def warp_errors(dtype, name, B, M):

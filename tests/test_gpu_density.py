@@ -15,8 +15,9 @@ import numpy as np
 import pytest
 import torch
 
-import test_density_host as H
-from test_density_host import GRID, ONE, PAIR, RADIAL, TOL, replica, walkers
+import replicas as H
+import support
+from replicas import GRID, ONE, PAIR, RADIAL, TOL, replica, walkers
 
 pytestmark = pytest.mark.gpu
 
@@ -28,11 +29,10 @@ _CTX, _REF = {}, {}
 def _ctx(name, dtype):
     if (name, dtype) not in _CTX:
         from oracle import system
-        from aiqmc import _lib
         atoms, per, spins = H.geometry(name)
         s = system.make_system(name)
         assert np.array_equal(s.atoms, atoms) and np.array_equal(s.spins, spins)
-        _CTX[(name, dtype)] = _lib.Context.for_system(s, dtype, atoms=atoms)
+        _CTX[(name, dtype)] = support.make_ctx(s, dtype, atoms=atoms)
     return _CTX[(name, dtype)]
 
 

@@ -13,17 +13,15 @@ import numpy as np
 import pytest
 import torch
 
+import support
+
 pytestmark = pytest.mark.gpu
 
 
 def _ctx(name, dtype, params_seed=5):
     from oracle import system
-    from aiqmc import _lib
     s = system.make_system(name)
-    ctx = _lib.Context.for_system(s, dtype)
-    p = system.init_params(np.random.default_rng(params_seed), s, randomize_aux=True)
-    ctx.set_params(system.flatten_params(p))
-    return s, ctx
+    return s, support.make_ctx(s, dtype, system.init_params(np.random.default_rng(params_seed), s, randomize_aux=True))
 
 
 def _walkers(s, B, seed=0):

@@ -19,6 +19,8 @@ import numpy as np
 import pytest
 import torch
 
+import support
+
 pytestmark = pytest.mark.gpu
 
 TAU = 0.05
@@ -26,13 +28,10 @@ TAU = 0.05
 
 def _ctx(dtype=torch.float32, flat=None):
     from oracle import system
-    from aiqmc import _lib
     s = system.make_system("N2")
-    ctx = _lib.Context.for_system(s, dtype)
     if flat is None:
         flat = system.flatten_params(system.init_params(np.random.default_rng(5), s, randomize_aux=True))
-    ctx.set_params(flat)
-    return s, ctx
+    return s, support.make_ctx(s, dtype, flat)
 
 
 def _reference_factor(x: np.ndarray, tau: float) -> float:

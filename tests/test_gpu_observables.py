@@ -19,13 +19,13 @@ Tolerances (none of them new):
   S2_L  the per-pair bounds weighted by |ratio| and summed over the walker's pairs.
 """
 import os
-import socket
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
+
+import support
+from replicas_estimators import TOL
 
 pytestmark = pytest.mark.gpu
 
@@ -35,8 +35,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 POLARISED = ["Z4@dudd", "Z5@uuuud", "Z9@uuuuduuuu"]
 CASES = ["H2", "Be", "Z5", "Z4-4", "Z9", "N2"] + POLARISED
 BMAX = 8
-# (rtol, atol) of dlogabs and atol of cos / sin of dphase: the single-value bounds, doubled
-TOL = {torch.float64: (2e-10, 2e-10, 2e-9), torch.float32: (2e-5, 4e-4, 4e-4)}
 
 _REF = {}
 
@@ -80,13 +78,8 @@ def _case(name):
 
 
 def _ctx(s, params, dtype):
-    from oracle import system
-    from aiqmc import _lib
-    if (s.nelectrons, s.natoms) not in _lib.supported_shapes():
-        pytest.skip(f"({s.nelectrons}, {s.natoms}) not in this library's shape list")
-    ctx = _lib.Context.for_system(s, dtype)
-    ctx.set_params(system.flatten_params(params))
-    return ctx
+    support.skip_unbuilt(s)
+    return support.make_ctx(s, dtype, params)
 
 
 @pytest.mark.parametrize("B", [5, 8])
@@ -285,16 +278,8 @@ def test_two_rank_pooled_mean_equals_one_process(tmp_path):
     """Two gloo ranks on the one test GPU (the pattern of tests/test_gpu_sharded.py), four Be walkers
     each: the pooled <S^2> and its variance equal the one-process values over all eight."""
     world = 2
-    with socket.socket() as sk:
-        sk.bind(("127.0.0.1", 0))
-        port = sk.getsockname()[1]
-    procs = []
-    for r in range(world):
-        env = dict(os.environ, RANK=str(r), WORLD_SIZE=str(world), LOCAL_RANK=str(r), MASTER_ADDR="127.0.0.1",
-                   MASTER_PORT=str(port), HSA_ENABLE_IPC_MODE_LEGACY="0")
-        procs.append(subprocess.Popen([sys.executable, "-c", _WORKER, ROOT, str(tmp_path)], env=env))
-    for p in procs:
-        assert p.wait(timeout=240) == 0
+    assert support.run_ranks(_WORKER, world, [ROOT, str(tmp_path)], timeout=240,
+                             env={"HSA_ENABLE_IPC_MODE_LEGACY": "0"}) == [0] * world
     outs = [dict(np.load(tmp_path / f"s2_{r}.npz")) for r in range(world)]
     full = _rank_s2(0, 1).cpu().numpy()
     np.testing.assert_array_equal(np.concatenate([o["s2"] for o in outs]), full)

@@ -6,19 +6,14 @@ import numpy as np
 import pytest
 import torch
 
+import support
+
 pytestmark = pytest.mark.gpu
 
 
 def _setup(name, dtype, B=4, seed=41):
-    from oracle import system
-    from aiqmc import _lib
-    s = system.make_system(name)
-    ctx = _lib.Context.for_system(s, dtype)
-    rng = np.random.default_rng(seed)
-    params = system.init_params(rng, s, randomize_aux=True)
-    ctx.set_params(system.flatten_params(params))
-    pos = system.init_electrons(rng, s.atoms, s.charges, B, 1.0)
-    return s, ctx, params, pos
+    s, params, pos = support.seeded_case(name, seed, B, randomize_aux=True)
+    return s, support.make_ctx(s, dtype, params), params, pos
 
 
 @pytest.mark.parametrize("name", ["H2", "Be", "N2"])

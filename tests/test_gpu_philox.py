@@ -29,6 +29,7 @@ import numpy as np
 import pytest
 import torch
 
+import support
 from oracle import philox
 
 pytestmark = pytest.mark.gpu
@@ -69,14 +70,9 @@ def _walkers(name, B, seed=2, width=1.0):
 
 
 def _ctx(name, dtype, packed=True, ecp=False):
-    from aiqmc import _lib
+    from oracle import pphamiltonian as pp
     s, flat = _setup(name)
-    ctx = _lib.Context.for_system(s, dtype)
-    if ecp:
-        from oracle import pphamiltonian as pp
-        e = pp.c_atom_ccecp()
-        ctx.set_ecp_tables(e)
-    ctx.set_params(flat)
+    ctx = support.make_ctx(s, dtype, flat, ecp=pp.c_atom_ccecp() if ecp else None)
     if not packed:
         ctx.set_packed_walkers(False)
     return s, ctx
@@ -90,14 +86,6 @@ def _x0(name, B, dtype, seed=2, width=1.0):
 def _ref_draws(seed, offset, B, N):
     g1, g2, u = philox.mc_draws(seed, offset, 1, B, N)
     return g1[0], g2[0], u[0]
-
-
-def _np(t):
-    return t.detach().cpu().numpy()
-
-
-def _same_bits(a, b):
-    return a.dtype == b.dtype and a.shape == b.shape and torch.equal(a, b)
 
 
 # ----------------------------------------------------------------------------- a. draws == replica
@@ -120,11 +108,11 @@ def test_sweep_draws_equal_the_replica(row):
         torch.cuda.synchronize()
         assert g1.shape == (B, 3 * N) and g2.shape == (B, N, 3) and u.shape == (B, N) and u.dtype == dtype
         r1, r2, ru = _ref_draws(seed, offset, B, N)
-        d1 = float(np.max(np.abs(_np(g1).astype(np.float64) - r1)))
-        d2 = float(np.max(np.abs(_np(g2).astype(np.float64) - r2)))
+        d1 = float(np.max(np.abs(support.to_np(g1).astype(np.float64) - r1)))
+        d2 = float(np.max(np.abs(support.to_np(g2).astype(np.float64) - r2)))
         print(f"philox draws {_id(row)} seed {seed} offset {offset}: max |g1 - ref| {d1:.3e} |g2 - ref| {d2:.3e}")
         worst = max(worst, d1, d2)
-        assert np.array_equal(_np(u).astype(np.float64), ru), (seed, offset)
+        assert np.array_equal(support.to_np(u).astype(np.float64), ru), (seed, offset)
         assert d1 <= NORMAL_BOUND and d2 <= NORMAL_BOUND, (seed, offset, d1, d2)
         assert bool(torch.isfinite(pos).all())
     print(f"philox draws {_id(row)}: worst normal deviation {worst:.3e}")
@@ -153,7 +141,7 @@ def test_philox_mc_step_equals_host_mode_fed_the_device_draws(row):
     g1, g2, u = (torch.stack([g[j] for g in got]) for j in range(3))
     torch.cuda.synchronize()
     for k in range(3):    # the scratch draws are the replica's (u exactly), so this feeds what (a) pinned
-        assert np.array_equal(_np(u[k]).astype(np.float64), _ref_draws(MC_SEED, MC_OFFSET + k, B, N)[2])
+        assert np.array_equal(support.to_np(u[k]).astype(np.float64), _ref_draws(MC_SEED, MC_OFFSET + k, B, N)[2])
 
     _, b = _ctx(name, dtype, packed)
     xb = _x0(name, B, dtype)
@@ -169,8 +157,8 @@ def test_philox_mc_step_equals_host_mode_fed_the_device_draws(row):
         xa = _x0(name, B, dtype)
         ca = a.mc_step(xa, 3, MC_TSTEP, seed=MC_SEED, offset=MC_OFFSET, count_accepts=True)
         torch.cuda.synchronize()
-        assert _same_bits(ca, cb), (fuse, _np(ca), _np(cb))
-        assert _same_bits(xa, xb), (fuse, float((xa - xb).abs().max()))
+        assert support.same_bits(ca, cb), (fuse, support.to_np(ca), support.to_np(cb))
+        assert support.same_bits(xa, xb), (fuse, float((xa - xb).abs().max()))
 
 
 # ----------------------------------------------------------------------------- c. DMC drift-diffusion
@@ -183,15 +171,15 @@ def test_philox_drift_diffusion_equals_host_mode_fed_the_device_draws(name, dtyp
     go_a, gn_a, td_a = a.dmc_drift_diffusion(xa, 0.05, seed=9, offset=2 ** 32 + 4)
     g1, g2, u = a.last_draws(B)
     torch.cuda.synchronize()
-    assert np.array_equal(_np(u).astype(np.float64), _ref_draws(9, 2 ** 32 + 4, B, N)[2])
+    assert np.array_equal(support.to_np(u).astype(np.float64), _ref_draws(9, 2 ** 32 + 4, B, N)[2])
     _, b = _ctx(name, dtype)
     xb = _x0(name, B, dtype)
     go_b, gn_b, td_b = b.dmc_drift_diffusion(xb, 0.05, gauss1=g1[None], gauss2=g2[None], u=u[None])
     torch.cuda.synchronize()
     assert bool((xa != _x0(name, B, dtype)).any())
-    assert _same_bits(xa, xb), float((xa - xb).abs().max())
-    assert _same_bits(go_a, go_b) and _same_bits(gn_a, gn_b)
-    assert _same_bits(td_a, td_b), (_np(td_a), _np(td_b))
+    assert support.same_bits(xa, xb), float((xa - xb).abs().max())
+    assert support.same_bits(go_a, go_b) and support.same_bits(gn_a, gn_b)
+    assert support.same_bits(td_a, td_b), (support.to_np(td_a), support.to_np(td_b))
     assert bool(torch.isfinite(go_a).all() and torch.isfinite(gn_a).all() and torch.isfinite(td_a).all())
 
 
@@ -211,7 +199,7 @@ def test_philox_rotations_equal_the_replica(dtype):
     R = ctx.last_rotations(ECP_B)
     torch.cuda.synchronize()
     assert R.shape == (ECP_B, 3, 3) and R.dtype == dtype
-    Rn = _np(R).astype(np.float64)
+    Rn = support.to_np(R).astype(np.float64)
     ref = philox.haar_rotations(5, 2, ECP_B)
     dev = float(np.max(np.abs(Rn - ref)))
     orth = float(np.max(np.abs(np.einsum("bij,bkj->bik", Rn, Rn) - np.eye(3))))
@@ -222,7 +210,7 @@ def test_philox_rotations_equal_the_replica(dtype):
     e2 = ctx.local_energy_ecp(pos, rot=R)
     torch.cuda.synchronize()
     assert bool(torch.isfinite(e.real).all() and torch.isfinite(e.imag).all())
-    assert _same_bits(e, e2), float((e - e2).abs().max())
+    assert support.same_bits(e, e2), float((e - e2).abs().max())
 
 
 # ----------------------------------------------------------------------------- e. T-moves
@@ -245,15 +233,15 @@ def test_philox_tmoves_equal_host_mode_fed_the_replica_uniforms(dtype):
     acc_a = ctx.dmc_tmoves(xa, 0.3, seed=7, offset=1)
     R = ctx.last_rotations(ECP_B)
     torch.cuda.synchronize()
-    np.testing.assert_allclose(_np(R).astype(np.float64), philox.haar_rotations(7, 1, ECP_B), rtol=0, atol=NORMAL_BOUND)
+    np.testing.assert_allclose(support.to_np(R).astype(np.float64), philox.haar_rotations(7, 1, ECP_B), rtol=0, atol=NORMAL_BOUND)
     us, ua = philox.tmove_draws(7, 1, ECP_B, N)
     xb = x0.clone()
     acc_b = ctx.dmc_tmoves(xb, 0.3, rot=R, u_sel=torch.tensor(us), u_acc=torch.tensor(ua))
     torch.cuda.synchronize()
     moved = int(((xa != x0).reshape(ECP_B, N, 3).any(dim=-1)).sum())
     print(f"philox tmoves {dtype}: {moved} of {ECP_B * N} electrons moved")
-    assert _same_bits(xa, xb), float((xa - xb).abs().max())
-    assert _same_bits(acc_a, acc_b)
+    assert support.same_bits(xa, xb), float((xa - xb).abs().max())
+    assert support.same_bits(acc_a, acc_b)
     assert bool(torch.isfinite(acc_a).all())
     assert moved >= 1
 

@@ -37,9 +37,13 @@ Shapes of 1-2: (14, 2) the benchmark's; (13, 2) and (16, 3) the edges of the MFM
 register layout; (12, 2) RW = 3 with the last row group full; (5, 1), which there runs
 k_moved_electron and the packed proposals.
 """
+import functools
+
 import numpy as np
 import pytest
 import torch
+
+import support
 
 pytestmark = pytest.mark.gpu
 
@@ -49,32 +53,18 @@ TSTEP = 0.05
 _ids = lambda sh: f"N{sh[0]}A{sh[1]}"
 
 
-def _name(n, a):
-    """charges: N split over the A atoms, the remainder on the first ones (as test_gpu_shapes.py)."""
-    zs = [n // a + (1 if k < n % a else 0) for k in range(a)]
-    return "Z" + "-".join(str(z) for z in zs)
-
-
-_SYS = {}
-
-
+@functools.lru_cache(maxsize=None)
 def _system(shape):
     """(system, params, oracle network, oracle params), cached per shape."""
-    if shape not in _SYS:
-        from oracle import network, system
-        n, a = shape
-        s = system.make_system(_name(n, a))
-        params = system.init_params(np.random.default_rng(800 + 3 * n + a), s, randomize_aux=True)
-        _SYS[shape] = (s, params, network.Network(s), network.to_torch(params))
-    return _SYS[shape]
+    from oracle import network
+    n, a = shape
+    s, params, _ = support.seeded_case(support.z_name(n, a), 800 + 3 * n + a, randomize_aux=True)
+    return s, params, network.Network(s), network.to_torch(params)
 
 
 def _ctx(shape, dtype, reuse=True):
-    from oracle import system
-    from aiqmc import _lib
     s, params, _, _ = _system(shape)
-    ctx = _lib.Context.for_system(s, dtype)
-    ctx.set_params(system.flatten_params(params))
+    ctx = support.make_ctx(s, dtype, params)
     ctx.set_proposal_reuse(reuse)
     return ctx
 
@@ -188,10 +178,7 @@ def _oracle_sweeps(shape, B, nsweeps):
         pos = system.init_electrons(np.random.default_rng(29 + n), s.atoms, s.charges, B, 1.0)
         found = None
         for seed in range(48):
-            rng = np.random.default_rng(seed)
-            g1 = torch.tensor(rng.standard_normal((nsweeps, B, 3 * n)))
-            g2 = torch.tensor(rng.standard_normal((nsweeps, B, n, 3 * n)))
-            u = torch.tensor(rng.uniform(size=(nsweeps, B, n)))
+            g1, g2, u = support.host_draws(seed, B, n, nsweeps)
             x, conds, gap = torch.tensor(pos), [], 1.0
             for k in range(nsweeps):
                 x, acc = mcstep.walkers_update(net, pt, x, g1[k], g2[k], u[k], TSTEP)

@@ -10,7 +10,6 @@ the same kernels with no process group.  The two-rank Adam step runs over gloo o
 """
 import json
 import os
-import socket
 import subprocess
 import sys
 
@@ -18,16 +17,12 @@ import numpy as np
 import pytest
 import torch
 
+import support
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "ab-initio-flexible-gaussian-basis-neural-network-quantum-monte-carlo_amd")
-
-
-def _free_port():
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
 
 
 def _be_training(B, dtype=torch.float64, lo=0, hi=None, seed=7):
@@ -167,7 +162,7 @@ def test_rccl_one_rank_group_is_bitwise_identity(tmp_path):
     gradient agrees with the one-rank fused kernel (aiqmc_loss_weights) to rounding."""
     f = tmp_path / "rccl.npz"
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    r = subprocess.run([sys.executable, "-c", _RCCL_WORKER, ROOT, PKG, str(f), str(_free_port())], env=env,
+    r = subprocess.run([sys.executable, "-c", _RCCL_WORKER, ROOT, PKG, str(f), str(support.free_port())], env=env,
                        capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-3000:]
     o = dict(np.load(f))
@@ -203,7 +198,7 @@ def test_bench_force_collectives_over_rccl_under_torchrun(tmp_path):
     """bench.py under torch.distributed.run --nproc-per-node 1 with --force-collectives: the VMC
     statistics all-reduce and the Be Adam side measurement's fused training step run in RCCL."""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr",
-           "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "1",
+           "127.0.0.1", "--master-port", str(support.free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "1",
            "--force-collectives", "--dist-backend", "nccl", "--steps", "2", "--warmup", "1", "--full",
            "--no-cpu-baseline", "--no-ecp", "--no-dmc", "--no-per-rank"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=str(tmp_path),
@@ -249,14 +244,8 @@ def test_two_rank_adam_step_equals_concatenated_batch(tmp_path, world):
     with a contiguous half of 128 walkers: 3 all-reduces per rank, and the parameters, loss,
     variance and clipped energies equal one process on all 128 walkers."""
     B = 128
-    port = _free_port()
-    procs = []
-    for r in range(world):
-        env = dict(os.environ, RANK=str(r), WORLD_SIZE=str(world), LOCAL_RANK=str(r), MASTER_ADDR="127.0.0.1",
-                   MASTER_PORT=str(port), HSA_ENABLE_IPC_MODE_LEGACY="0")
-        procs.append(subprocess.Popen([sys.executable, "-c", _ADAM_WORKER, ROOT, PKG, str(tmp_path), str(B)], env=env))
-    for p in procs:
-        assert p.wait(timeout=240) == 0
+    assert support.run_ranks(_ADAM_WORKER, world, [ROOT, PKG, str(tmp_path), str(B)], timeout=240,
+                             env={"HSA_ENABLE_IPC_MODE_LEGACY": "0"}) == [0] * world
     from aiqmc.wavefunction_Ynlm import nn
     s, network, params, data, ev, step, le = _be_training(B, torch.float64)
     _, p_ref, _, loss_ref, aux_ref = step(data, params, None, 0)

@@ -31,8 +31,8 @@ import numpy as np
 import pytest
 import torch
 
-from test_gpu_observables import TOL
-from test_rdm_host import C0, C1, _shells
+import support
+from replicas_estimators import C0, C1, TOL, _shells
 
 pytestmark = pytest.mark.gpu
 
@@ -147,22 +147,13 @@ def reference(s, basis, pos, rp, w, dl, dp, dtype):
 
 
 def _ctx(s, params, dtype, kind=None):
-    from oracle import system
-    from aiqmc import _lib
-    if (s.nelectrons, s.natoms) not in _lib.supported_shapes():
-        pytest.skip(f"({s.nelectrons}, {s.natoms}) not in this library's shape list")
-    ctx = _lib.Context.for_system(s, dtype)
-    if params is not None:
-        ctx.set_params(system.flatten_params(params))
+    support.skip_unbuilt(s)
+    ctx = support.make_ctx(s, dtype, params)
     if kind is not None:
         b, q = _basis(kind)
         ctx.set_rdm_basis(b.shell_l, b.shell_nprim, b.shell_center, b.exps, b.coefs, b.mo_coeff, q.centres, q.sigmas,
                           q.probs)
     return ctx
-
-
-def _dev(a, dtype):
-    return torch.tensor(a, device="cuda", dtype=dtype)
 
 
 CASES = [("H2", 5), ("H2", 8), ("H2", 37), ("Z5", 5), ("Z5", 8), ("N2", 5), ("N2", 8)] + [(n, B) for n in POLARISED
@@ -178,8 +169,8 @@ def test_matrix_matches_oracle(dtype, name, B, kind):
     wb = w[:B] if B == 5 else None                     # B = 5 runs weighted, the others with unit weights
     ref, bound = reference(s, basis, pos[:B], rp[:B], wb, dl[:B], dp[:B], dtype)
     ctx = _ctx(s, params, dtype, kind)
-    acc = ctx.rdm_accumulate(_dev(pos[:B], dtype), SAMPLES[name], rprime=_dev(rp[:B], dtype),
-                             weights=None if wb is None else _dev(wb, dtype))
+    acc = ctx.rdm_accumulate(support.dev(pos[:B], dtype), SAMPLES[name], rprime=support.dev(rp[:B], dtype),
+                             weights=None if wb is None else support.dev(wb, dtype))
     torch.cuda.synchronize()
     got = acc.cpu().numpy()
     assert got.shape == (1 + 4 * basis.norb ** 2,)
@@ -215,13 +206,13 @@ def test_ratios_are_logpsi_differences_bitwise(dtype, name):
     s, params, pos, rp, _, _, _ = _case(name)
     B, S, N = 5, SAMPLES[name], s.nelectrons
     ctx = _ctx(s, params, dtype, "p3")
-    x = _dev(pos[:B], dtype)
-    xm = _dev(_REF[name][7][:B].reshape(-1, 3 * N), dtype)
-    _, rpo, ro = ctx.rdm_accumulate(x, S, rprime=_dev(rp[:B], dtype), want_points=True, want_ratios=True)
+    x = support.dev(pos[:B], dtype)
+    xm = support.dev(_REF[name][7][:B].reshape(-1, 3 * N), dtype)
+    _, rpo, ro = ctx.rdm_accumulate(x, S, rprime=support.dev(rp[:B], dtype), want_points=True, want_ratios=True)
     la0, ph0 = ctx.logpsi(x)
     la1, ph1 = ctx.logpsi(xm)
     torch.cuda.synchronize()
-    assert ro.shape == (B, S, N, 2) and torch.equal(rpo, _dev(rp[:B], dtype))
+    assert ro.shape == (B, S, N, 2) and torch.equal(rpo, support.dev(rp[:B], dtype))
     assert torch.equal(ro[..., 0].reshape(B, S * N), la1.reshape(B, S * N) - la0[:, None])
     assert torch.equal(ro[..., 1].reshape(B, S * N), ph1.reshape(B, S * N) - ph0[:, None])
 
@@ -238,14 +229,14 @@ def test_basis_values_match_numpy(dtype, kind):
     pts = _f32(np.random.default_rng(23).standard_normal((70, 3)) * 1.5)
     u = 2.0 ** -24 if dtype == F32 else 2.0 ** -53
     for spin in (0, 1):
-        got = ctx.rdm_basis_values(_dev(pts, dtype), spin).double().cpu().numpy()
+        got = ctx.rdm_basis_values(support.dev(pts, dtype), spin).double().cpu().numpy()
         ref, mag, g64 = basis_np(basis, pts, spin)
         n = basis.nao + 1
         bound = (n * u / (1 - n * u) + g64) * mag
         assert got.shape == ref.shape == (70, basis.norb)
         print(f"{kind} {dtype} spin {spin}: max |err| / bound {np.max(np.abs(got - ref) / bound):.3g}")
         assert np.all(np.abs(got - ref) <= bound)
-    assert ctx.rdm_basis_values(_dev(pts[:0], dtype)).shape == (0, basis.norb)
+    assert ctx.rdm_basis_values(support.dev(pts[:0], dtype)).shape == (0, basis.norb)
 
 
 @pytest.mark.parametrize("name,B", [("H2", 37), ("Z5", 5)])
@@ -258,7 +249,7 @@ def test_philox_points_and_injection(dtype, name, B):
     S = SAMPLES[name]
     _, q = _basis("spd17")
     ctx = _ctx(s, params, dtype, "spd17")
-    x, wd = _dev(pos[:B], dtype), _dev(w[:B], dtype)
+    x, wd = support.dev(pos[:B], dtype), support.dev(w[:B], dtype)
     u = 2.0 ** -24 if dtype == F32 else 2.0 ** -53
     for seed, step in ((5, 0), (2 ** 32 + 7, 2 ** 32 + 3)):
         a, rpo = ctx.rdm_accumulate(x, S, seed=seed, step=step, weights=wd, want_points=True)
@@ -280,7 +271,7 @@ def test_chunking_repeats_and_accumulate_are_bitwise(dtype):
     chunks with a partial second one.  accumulate = 1 after accumulate = 0 on one group doubles every entry."""
     s, params, pos, rp, w, _, _ = _case("H2")
     ctx = _ctx(s, params, dtype, "spd17")
-    x, r, wd = _dev(pos, dtype), _dev(rp, dtype), _dev(w, dtype)
+    x, r, wd = support.dev(pos, dtype), support.dev(rp, dtype), support.dev(w, dtype)
     one = ctx.rdm_accumulate(x, 3, rprime=r, weights=wd, want_ratios=True)
     many = ctx.rdm_accumulate(x, 3, rprime=r, weights=wd, want_ratios=True, chunk=224)
     tiny = ctx.rdm_accumulate(x, 3, rprime=r, weights=wd, want_ratios=True, chunk=1)    # still whole groups
@@ -311,7 +302,7 @@ def test_drop_in_accumulator_equals_the_context_call(dtype):
     rp = _f32(rng.standard_normal((B, S, 3)))
     w = _f32(rng.uniform(0.5, 1.5, B))
     basis, q = _basis("spd17")
-    x, r, wd = _dev(pos, dtype), _dev(rp, dtype), _dev(w, dtype)
+    x, r, wd = support.dev(pos, dtype), support.dev(rp, dtype), support.dev(w, dtype)
     data = nn.AINetData(positions=x, spins=s.spins, atoms=s.atoms, charges=s.charges)
     acc = obs.make_density_matrix(net.apply, s.nspins, basis, q=q, samples=S)
     acc.update(params, data, r, weights=wd)
@@ -334,7 +325,7 @@ def test_drop_in_accumulator_equals_the_context_call(dtype):
 
 def test_empty_batch_missing_params_and_missing_basis():
     s, params, pos, rp, _, _, _ = _case("H2")
-    x, r = _dev(pos[:4], F64), _dev(rp[:4], F64)
+    x, r = support.dev(pos[:4], F64), support.dev(rp[:4], F64)
     with pytest.raises(RuntimeError, match="set_params"):
         _ctx(s, None, F64, "p3").rdm_accumulate(x, 3, rprime=r)
     ctx = _ctx(s, params, F64)

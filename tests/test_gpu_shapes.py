@@ -20,54 +20,25 @@ import numpy as np
 import pytest
 import torch
 
+import support
+
 pytestmark = pytest.mark.gpu
 
 # the Makefile's SHAPES; a shape the loaded library does not list (a development build) is skipped
 SHAPES = [(n, a) for a in (1, 2, 3) for n in range(max(2, a), 17)] + [(10, 4), (10, 5)]
 
 
-def _name(n, a):
-    """charges: N split over the A atoms, the remainder on the first ones."""
-    zs = [n // a + (1 if k < n % a else 0) for k in range(a)]
-    return "Z" + "-".join(str(z) for z in zs)
-
-
-def _skip_unbuilt(shape):
-    from aiqmc import _lib
-    if tuple(shape) not in _lib.supported_shapes():
-        pytest.skip(f"{shape} not in this library's shape list")
-
-
-_REF = {}
-
-
 def _oracle(n, a):
     """(system, params, pos, e_l, logabs, grad) of the fp64 oracle, cached per shape."""
-    _skip_unbuilt((n, a))
-    if (n, a) not in _REF:
-        from oracle import hamiltonian, network, system
-        s = system.make_system(_name(n, a))
-        rng = np.random.default_rng(100 + 3 * n + a)
-        params = system.init_params(rng, s, randomize_aux=True)
-        pos = system.init_electrons(rng, s.atoms, s.charges, 4 if n <= 10 else 2, 1.0)
-        e, l, g = hamiltonian.batch_local_energy(network.Network(s), network.to_torch(params), torch.tensor(pos))
-        _REF[(n, a)] = (s, params, pos, e.numpy(), l.numpy(), g.numpy())
-    return _REF[(n, a)]
-
-
-def _ctx(s, params, dtype):
-    from oracle import system
-    from aiqmc import _lib
-    ctx = _lib.Context.for_system(s, dtype)
-    ctx.set_params(system.flatten_params(params))
-    return ctx
+    support.skip_unbuilt((n, a))
+    return support.oracle_case(support.z_name(n, a), 100 + 3 * n + a, randomize_aux=True)
 
 
 @pytest.mark.parametrize("shape", SHAPES, ids=lambda sh: f"N{sh[0]}A{sh[1]}")
 def test_shape_fp64_matches_oracle(shape):
     s, params, pos, e_ref, l_ref, g_ref = _oracle(*shape)
     assert (s.nelectrons, s.natoms) == shape
-    ctx = _ctx(s, params, torch.float64)
+    ctx = support.make_ctx(s, torch.float64, params)
     x = torch.tensor(pos, device="cuda")
     e, l, g = ctx.local_energy(x, want_logabs=True, want_grad=True)
     l2, g2 = ctx.logpsi_grad(x)
@@ -84,7 +55,7 @@ def test_shape_metropolis_and_param_grad_match_oracle(shape):
     from oracle import loss, mcstep, network
     s, params, pos, _, _, _ = _oracle(*shape)
     N, B = s.nelectrons, pos.shape[0]
-    ctx = _ctx(s, params, torch.float64)
+    ctx = support.make_ctx(s, torch.float64, params)
     rng = np.random.default_rng(7 + N)
     g1 = torch.tensor(rng.standard_normal((1, B, 3 * N)))
     g2 = torch.tensor(rng.standard_normal((1, B, N, 3 * N)))
@@ -105,7 +76,7 @@ def test_shape_metropolis_and_param_grad_match_oracle(shape):
 @pytest.mark.parametrize("shape", SHAPES, ids=lambda sh: f"N{sh[0]}A{sh[1]}")
 def test_shape_fp32_matches_oracle(shape):
     s, params, pos, e_ref, l_ref, _ = _oracle(*shape)
-    ctx = _ctx(s, params, torch.float32)
+    ctx = support.make_ctx(s, torch.float32, params)
     x = torch.tensor(pos, device="cuda").float().contiguous()
     e, l, _ = ctx.local_energy(x, want_logabs=True, want_grad=True)
     torch.cuda.synchronize()
@@ -160,19 +131,16 @@ def test_shape_fp32_sweeps_follow_fp64(shape):
     proposal path) against fp64 sweeps from the same float-rounded walkers and host draws: at most
     one acceptance decision in 100 flips, and the walkers that took the same decisions agree to
     fp32 rounding."""
-    from oracle import system
     n, a = shape
-    _skip_unbuilt(shape)
-    s = system.make_system(_name(n, a))
-    rng = np.random.default_rng(5 + n)
-    params = system.init_params(rng, s, randomize_aux=True)
+    support.skip_unbuilt(shape)
     B, NS = 64, 3
-    pos = system.init_electrons(rng, s.atoms, s.charges, B, 1.0).astype(np.float32).astype(np.float64)
+    s, params, pos = support.seeded_case(support.z_name(n, a), 5 + n, B, randomize_aux=True)
+    pos = pos.astype(np.float32).astype(np.float64)
     g = torch.Generator().manual_seed(n + 10 * a)
     kw = dict(gauss1=torch.randn(NS, B, 3 * n, generator=g, dtype=torch.float64),
               gauss2=torch.randn(NS, B, n, 3, generator=g, dtype=torch.float64),
               u=torch.rand(NS, B, n, generator=g, dtype=torch.float64))
-    c64, c32 = _ctx(s, params, torch.float64), _ctx(s, params, torch.float32)
+    c64, c32 = support.make_ctx(s, torch.float64, params), support.make_ctx(s, torch.float32, params)
     x64 = torch.tensor(pos, device="cuda").contiguous()
     x32 = x64.float().contiguous()
     a64 = c64.mc_step(x64, NS, 0.05, count_accepts=True, **kw)
@@ -197,8 +165,8 @@ def test_param_grad_partial_last_wave(shape, B):
     vs the oracle and fp32 vs fp64, on such batches."""
     from oracle import loss, network, system
     n, a = shape
-    _skip_unbuilt(shape)
-    s = system.make_system(_name(n, a))
+    support.skip_unbuilt(shape)
+    s = system.make_system(support.z_name(n, a))
     rng = np.random.default_rng(40 + n + a)
     params = system.init_params(rng, s, randomize_aux=True)
     pos = system.init_electrons(rng, s.atoms, s.charges, B, 1.0)
@@ -206,7 +174,7 @@ def test_param_grad_partial_last_wave(shape, B):
     O_ref = loss.logabs_param_grad(net, params, torch.tensor(pos))
     P_ref = loss.phase_param_grad(net, params, torch.tensor(pos))
     w = rng.normal(size=B)
-    c64, c32 = _ctx(s, params, torch.float64), _ctx(s, params, torch.float32)
+    c64, c32 = support.make_ctx(s, torch.float64, params), support.make_ctx(s, torch.float32, params)
     x = torch.tensor(pos, device="cuda")
     for ref, fn in ((O_ref, "logpsi_param_grad"), (P_ref, "phase_param_grad")):
         rows = getattr(c64, fn)(x).cpu().numpy()
@@ -231,15 +199,15 @@ def test_set_params_device_equals_host_upload_shapes(shape, dtype):
     host upload."""
     from oracle import system
     n, a = shape
-    _skip_unbuilt(shape)
-    s = system.make_system(_name(n, a))
+    support.skip_unbuilt(shape)
+    s = system.make_system(support.z_name(n, a))
     rng = np.random.default_rng(60 + n + a)
     params = system.init_params(rng, s, randomize_aux=True)
     flat = system.flatten_params(params)
     pos = torch.tensor(system.init_electrons(rng, s.atoms, s.charges, 8, 1.0), device="cuda", dtype=dtype)
     outs = []
     for mode in ("host", "device"):
-        ctx = _ctx(s, params, dtype)
+        ctx = support.make_ctx(s, dtype, params)
         if mode == "device":   # over a different host upload, so a no-op device repack would fail
             ctx.set_params(0.5 * flat)
             ctx.set_params_device(torch.tensor(flat, dtype=torch.float64, device="cuda"))

@@ -12,7 +12,6 @@ torch.distributed.run with two ranks (the driver's multi-GPU launch line, gloo r
 """
 import json
 import os
-import socket
 import subprocess
 import sys
 
@@ -20,16 +19,12 @@ import numpy as np
 import pytest
 import torch
 
+import support
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 B_TOTAL, NSTEPS, TSTEP = 4096, 3, 0.05
-
-
-def _free_port():
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
 
 
 def _block(rank, world, b_total=B_TOTAL):
@@ -81,14 +76,8 @@ dist.destroy_process_group()
 def test_two_rank_blocks_equal_single_process(tmp_path, world, b_total):
     """(8, 32768): BASELINE config 4's walker count sharded 8 ways (4,096 per rank; the reference's
     KFAC leg is out of scope), eight gloo ranks on the one test GPU."""
-    port = _free_port()
-    procs = []
-    for r in range(world):
-        env = dict(os.environ, RANK=str(r), WORLD_SIZE=str(world), LOCAL_RANK=str(r), MASTER_ADDR="127.0.0.1",
-                   MASTER_PORT=str(port), HSA_ENABLE_IPC_MODE_LEGACY="0")
-        procs.append(subprocess.Popen([sys.executable, "-c", _WORKER, ROOT, str(tmp_path), str(b_total)], env=env))
-    for p in procs:
-        assert p.wait(timeout=240) == 0
+    assert support.run_ranks(_WORKER, world, [ROOT, str(tmp_path), str(b_total)], timeout=240,
+                             env={"HSA_ENABLE_IPC_MODE_LEGACY": "0"}) == [0] * world
     outs = [dict(np.load(tmp_path / f"rank{r}.npz")) for r in range(world)]
     from aiqmc import constants
     els = []
@@ -110,7 +99,7 @@ def test_two_rank_blocks_equal_single_process(tmp_path, world, b_total):
 
 def _bench_two_ranks(tmp_path, extra, n=2):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n), "--master-addr",
-           "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps",
+           "127.0.0.1", "--master-port", str(support.free_port()), os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps",
            "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-ecp", "--no-adam", "--no-dmc",
            "--dist-backend", "gloo"] + extra
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=str(tmp_path),
@@ -245,14 +234,8 @@ def test_two_rank_dmc_driver_matches_two_device_oracle(tmp_path, golden_dir, fix
     all-electron Ne (BASELINE config 5, Ne_dmc_ne_allelectron_2dev.npz), 2 walkers per rank."""
     world = 2
     fixture = os.path.join(golden_dir, fixture_name)
-    port = _free_port()
-    procs = []
-    for r in range(world):
-        env = dict(os.environ, RANK=str(r), WORLD_SIZE=str(world), LOCAL_RANK=str(r), MASTER_ADDR="127.0.0.1",
-                   MASTER_PORT=str(port), HSA_ENABLE_IPC_MODE_LEGACY="0")
-        procs.append(subprocess.Popen([sys.executable, "-c", _DMC_WORKER, ROOT, str(tmp_path), fixture], env=env))
-    for p in procs:
-        assert p.wait(timeout=240) == 0
+    assert support.run_ranks(_DMC_WORKER, world, [ROOT, str(tmp_path), fixture], timeout=240,
+                             env={"HSA_ENABLE_IPC_MODE_LEGACY": "0"}) == [0] * world
     g = dict(np.load(fixture))
     B = g["x0"].shape[0]
     Bd = B // world

@@ -42,6 +42,8 @@ import numpy as np
 import pytest
 import torch
 
+import support
+
 pytestmark = pytest.mark.gpu
 
 PACK4 = ["Z3@ddu", "Z4@uuud", "Z4@dudd", "Z2-2@uduu"]
@@ -56,39 +58,26 @@ TSTEP, SWEEPS = 0.05, 2
 # proposal in every sweep (at tstep 0.05 it accepts about 97 in 100; Z2-2@uduu: in the first sweep)
 MC_SEED = dict(zip(CASES, [1510, 11, 2211, 1211, 112, 813, 614, 514, 115, 16, 117, 120, 123]))
 
-_REF, _PG, _MC = {}, {}, {}
+_PG, _MC = {}, {}
 
 
 def _system(name):
     from oracle import system
-    from aiqmc import _lib
     s = system.make_system(name)
-    if (s.nelectrons, s.natoms) not in _lib.supported_shapes():
-        pytest.skip(f"({s.nelectrons}, {s.natoms}) not in this library's shape list")
+    support.skip_unbuilt(s)
     return s
 
 
 def _draw(name, B=None, seed=None):
     """(system, params, pos [B, 3N]) of a case: its seeded parameters and walkers."""
-    from oracle import system
-    s = _system(name)
-    rng = np.random.default_rng(700 + CASES.index(name) if seed is None else seed)
-    params = system.init_params(rng, s, randomize_aux=True)
-    if B is None:
-        B = 4 if s.nelectrons <= 10 else 2
-    return s, params, system.init_electrons(rng, s.atoms, s.charges, B, 1.0)
+    _system(name)
+    return support.seeded_case(name, 700 + CASES.index(name) if seed is None else seed, B, randomize_aux=True)
 
 
 def _oracle(name):
     """(system, params, pos, e_l, logabs, phase, grad) of the fp64 oracle, cached per case."""
-    if name not in _REF:
-        from oracle import hamiltonian, network
-        s, params, pos = _draw(name)
-        net, pt = network.Network(s), network.to_torch(params)
-        e, l, g = hamiltonian.batch_local_energy(net, pt, torch.tensor(pos))
-        ph = np.array([float(net.apply(pt, r)[0]) for r in torch.tensor(pos)])
-        _REF[name] = (s, params, pos, e.numpy(), l.numpy(), ph, g.numpy())
-    return _REF[name]
+    _system(name)
+    return support.oracle_case(name, 700 + CASES.index(name), randomize_aux=True, phase=True)
 
 
 def _param_grads(name):
@@ -108,10 +97,7 @@ def _metropolis(name):
         from oracle import mcstep, network
         s, params, pos = _oracle(name)[:3]
         N, B = s.nelectrons, pos.shape[0]
-        rng = np.random.default_rng(MC_SEED[name])
-        g1 = torch.tensor(rng.standard_normal((SWEEPS, B, 3 * N)))
-        g2 = torch.tensor(rng.standard_normal((SWEEPS, B, N, 3 * N)))
-        u = torch.tensor(rng.uniform(size=(SWEEPS, B, N)))
+        g1, g2, u = support.host_draws(MC_SEED[name], B, N, SWEEPS)
         net, pt = network.Network(s), network.to_torch(params)
         x, accepts = torch.tensor(pos), []
         for k in range(SWEEPS):
@@ -120,14 +106,6 @@ def _metropolis(name):
             accepts.append(int(info["cond"].sum()))
         _MC[name] = (g1, g2, u, x.numpy(), accepts)
     return _MC[name]
-
-
-def _ctx(s, params, dtype):
-    from oracle import system
-    from aiqmc import _lib
-    ctx = _lib.Context.for_system(s, dtype)
-    ctx.set_params(system.flatten_params(params))
-    return ctx
 
 
 def _ee_columns(s, params):
@@ -166,7 +144,7 @@ def test_case_is_the_partition_it_claims(name):
 @pytest.mark.parametrize("name", CASES)
 def test_polarised_fp64_matches_oracle(name):
     s, params, pos, e_ref, l_ref, ph_ref, g_ref = _oracle(name)
-    ctx = _ctx(s, params, torch.float64)
+    ctx = support.make_ctx(s, torch.float64, params)
     x = torch.tensor(pos, device="cuda")
     e, l, g = ctx.local_energy(x, want_logabs=True, want_grad=True)
     l2, g2 = ctx.logpsi_grad(x)
@@ -192,7 +170,7 @@ def test_polarised_two_metropolis_sweeps_match_oracle(name):
     # the oracle alone: the comparison is not vacuous, and the second sweep starts from walkers of
     # which some electrons moved and some did not
     assert 0 < accepts[0] < B * N and 0 < sum(accepts) < SWEEPS * B * N, (accepts, B * N)
-    ctx = _ctx(s, params, torch.float64)
+    ctx = support.make_ctx(s, torch.float64, params)
     idx = torch.arange(N)
     x = torch.tensor(pos, device="cuda").contiguous()
     ctx.mc_step(x, SWEEPS, TSTEP, gauss1=g1, gauss2=g2.reshape(SWEEPS, B, N, N, 3)[:, :, idx, idx, :].contiguous(), u=u)
@@ -204,7 +182,7 @@ def test_polarised_two_metropolis_sweeps_match_oracle(name):
 def test_polarised_param_grads_match_oracle(name):
     s, params, pos = _oracle(name)[:3]
     O_ref, P_ref = _param_grads(name)
-    ctx = _ctx(s, params, torch.float64)
+    ctx = support.make_ctx(s, torch.float64, params)
     x = torch.tensor(pos, device="cuda")
     _assert_rows(ctx.logpsi_param_grad(x).cpu().numpy(), O_ref, 1e-8, s, params, "logpsi_param_grad")
     _assert_rows(ctx.phase_param_grad(x).cpu().numpy(), P_ref, 1e-8, s, params, "phase_param_grad")
@@ -214,7 +192,7 @@ def test_polarised_param_grads_match_oracle(name):
 def test_polarised_fp32_matches_oracle(name):
     s, params, pos, e_ref, l_ref, _, _ = _oracle(name)
     O_ref, P_ref = _param_grads(name)
-    ctx = _ctx(s, params, torch.float32)
+    ctx = support.make_ctx(s, torch.float32, params)
     x = torch.tensor(pos, device="cuda").float().contiguous()
     e, l, _ = ctx.local_energy(x, want_logabs=True, want_grad=True)
     O, P = ctx.logpsi_param_grad(x), ctx.phase_param_grad(x)
@@ -235,7 +213,7 @@ def test_polarised_param_grad_partial_last_wave(name, B):
     s, params, pos = _draw(name, B=B, seed=40 + CASES.index(name))
     net = network.Network(s)
     w = np.random.default_rng(3).normal(size=B)
-    c64, c32 = _ctx(s, params, torch.float64), _ctx(s, params, torch.float32)
+    c64, c32 = support.make_ctx(s, torch.float64, params), support.make_ctx(s, torch.float32, params)
     x = torch.tensor(pos, device="cuda")
     for ref, fn in ((loss.logabs_param_grad(net, params, torch.tensor(pos)), "logpsi_param_grad"),
                     (loss.phase_param_grad(net, params, torch.tensor(pos)), "phase_param_grad")):
@@ -265,7 +243,7 @@ def test_polarised_ecp_local_energy_matches_oracle(name):
     rots = pp.haar_rotations(rng, B)
     ref, _, _, _ = pp.batch_local_energy_pp(network.Network(s), network.to_torch(params), ecp, torch.tensor(pos), rots)
     ref = ref.detach().numpy()
-    c64, c32 = _ctx(s, params, torch.float64), _ctx(s, params, torch.float32)
+    c64, c32 = support.make_ctx(s, torch.float64, params), support.make_ctx(s, torch.float32, params)
     c64.set_ecp_tables(ecp)
     c32.set_ecp_tables(ecp)
     e = c64.local_energy_ecp(torch.tensor(pos, device="cuda"), rot=torch.tensor(rots, device="cuda"))
@@ -301,7 +279,7 @@ def test_polarised_tmoves_match_oracle(table):
     new, acc = torch.stack(new).numpy(), np.stack(acc)
     if table == "attractive":
         assert (np.abs(new - pos).reshape(B, -1, 3).sum(-1) > 0).any()     # the oracle moves electrons
-    ctx = _ctx(s, params, torch.float64)
+    ctx = support.make_ctx(s, torch.float64, params)
     ctx.set_ecp_tables(ecp)
     x = torch.tensor(pos, device="cuda").contiguous()
     got = ctx.dmc_tmoves(x, tau, rot=torch.tensor(rots), u_sel=torch.tensor(u_sel), u_acc=torch.tensor(u_acc))
@@ -323,7 +301,7 @@ def test_polarised_fp32_sweeps_follow_fp64(name):
     kw = dict(gauss1=torch.randn(NS, B, 3 * n, generator=g, dtype=torch.float64),
               gauss2=torch.randn(NS, B, n, 3, generator=g, dtype=torch.float64),
               u=torch.rand(NS, B, n, generator=g, dtype=torch.float64))
-    c64, c32 = _ctx(s, params, torch.float64), _ctx(s, params, torch.float32)
+    c64, c32 = support.make_ctx(s, torch.float64, params), support.make_ctx(s, torch.float32, params)
     x64 = torch.tensor(pos, device="cuda").contiguous()
     x32 = x64.float().contiguous()
     a64 = c64.mc_step(x64, NS, TSTEP, count_accepts=True, **kw)

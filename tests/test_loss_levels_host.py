@@ -6,8 +6,8 @@ import numpy as np
 import pytest
 import torch
 
-from test_gpu_reductions import (CLIPS, DT_IDS, DTYPES, LOSS_B, SPLITS, _assert_stats, _check_edges, _check_levels,
-                                 _loss_energies, _loss_reference, _run_levels)
+from replicas_loss import (CLIPS, DT_IDS, DTYPES, LOSS_B, SPLITS, _assert_stats, _check_edges, _check_levels,
+                           _loss_energies, _loss_reference, _run_levels)
 
 
 def _final_host(L1, head, g0, center, world):

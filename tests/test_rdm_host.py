@@ -13,28 +13,17 @@ sigma^2 = 1 = 1 / (2 min(a, c)); a = 1, b = 0.8, c = 0.5, B = 2048, S = 2 and 16
 errors between 0.002 and 0.012 (run on the CPU, seed 11), below the 0.02 the test requires of itself.
 """
 import os
-import socket
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
+import support
 from conftest import ROOT
+from replicas_estimators import C0, C1, _shells  # noqa: F401
 
 # electrons 0 and 2 up, 1 down: unequal channels
 SPINS3 = np.array([1.0, -1.0, 1.0])
-C0, C1 = np.array([0.1, -0.2, 0.3]), np.array([-0.4, 0.5, 0.2])
-
-
-def _shells(obs):
-    """s, p and d shells on two centres (nao = 20), contracted and not."""
-    S = obs.Shell
-    return [S(C0, 0, [1.3, 0.4], obs.normalized_shell(0, [1.3, 0.4], [0.6, 0.5])), S(C0, 1, [0.9], [0.7]),
-            S(C0, 2, [0.7], obs.normalized_shell(2, [0.7], [1.0])),
-            S(C1, 0, [0.5], [1.1]), S(C1, 1, [1.1, 0.35], [0.3, -0.8]), S(C1, 2, [0.45, 0.8], [0.5, 0.25])]
-
 
 CART = {0: [(0, 0, 0)], 1: [(1, 0, 0), (0, 1, 0), (0, 0, 1)],
         2: [(2, 0, 0), (1, 1, 0), (1, 0, 1), (0, 2, 0), (0, 1, 1), (0, 0, 2)]}
@@ -304,16 +293,7 @@ dist.destroy_process_group()
 
 def test_two_rank_gloo_reduction_equals_one_process(tmp_path):
     world = 2
-    with socket.socket() as sk:
-        sk.bind(("127.0.0.1", 0))
-        port = sk.getsockname()[1]
-    procs = []
-    for r in range(world):
-        env = dict(os.environ, RANK=str(r), WORLD_SIZE=str(world), LOCAL_RANK=str(r), MASTER_ADDR="127.0.0.1",
-                   MASTER_PORT=str(port))
-        procs.append(subprocess.Popen([sys.executable, "-c", _WORKER, ROOT, str(tmp_path)], env=env))
-    for p in procs:
-        assert p.wait(timeout=240) == 0
+    assert support.run_ranks(_WORKER, world, [ROOT, str(tmp_path)], timeout=240) == [0] * world
     _, one = _small_case(updates=1)
     one.reduce()                                   # the identity in a single process
     n = one.n

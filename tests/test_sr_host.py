@@ -10,7 +10,6 @@ The loss is a stand-in with the attributes of a ``make_loss`` result that the op
 import math
 import os
 import re
-import socket
 import types
 
 import numpy as np
@@ -19,6 +18,7 @@ import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
+import support
 from conftest import ROOT
 
 P = 23
@@ -241,14 +241,6 @@ B_RANK = 48
 OPT_KW = dict(norm_constraint=1e-2, curvature_ema=0.9, min_damping=1e-4, l2_reg=0.01)
 
 
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
 def _run_steps(batches):
     from aiqmc.Optimizer import sr
     loss = StubLoss(True)
@@ -284,7 +276,7 @@ def _worker(rank, world, port, q):
 
 def test_two_ranks_equal_the_concatenated_batch():
     world = 2
-    port = _free_port()
+    port = support.free_port()
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     procs = [ctx.Process(target=_worker, args=(r, world, port, q)) for r in range(world)]
